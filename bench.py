@@ -3,9 +3,11 @@
 bwd + AdamW, 2 STFT + 1 iSTFT fwd + 1 iSTFT bwd) on synthetic 2 s / 16 kHz clips, batch 16 per MI355X
 (BASELINE.json configs[1]).  One process per GPU; N > 1 is launched by torch.distributed.run (RCCL).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement).  `roofline` is measured live
-with HIP events around every launch of the dominant kernel family during the timed steps; `cpu_baseline` times
-the CPU oracle (a torch-CPU port of the same step) on a bounded sample on the host cores (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline
+(`value`, `ms_per_step`, losses of the last timed step); `--dump-outputs DIR` also writes what the last timed step computed.
+`--full` adds everything else, measured after the timed steps: `roofline` (HIP events around every launch of each kernel family
+on extra steps), `clocks`, `secondary` configurations, and first of all `cpu_baseline`, which times the CPU oracle (a torch-CPU
+port of the same step) on a bounded sample on the host cores (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -96,15 +98,16 @@ def _family_entry(key, v, steps, pmc):
 def cpu_baseline(budget_s=48.0):
     """The CPU oracle's CMGAN train step (torch-CPU port of the reference step: AdamW, PESQ labels supplied) timed on the host cores.
     Protocol (bounded so that the default run stays within minutes): (1) thread sweep 16 / 32 / 64 / 128
-    (capped at the host's cores) on a generator-only forward, stopped at the first count that is slower than the best (torch-CPU
-    oversubscribes a 256-core host: on the round-6 box 16 threads 3.7 s, 64 5.3 s, 128 10.1 s -- the sweep says so in two forwards
-    instead of spending the budget proving it); (2) at the best
-    count: 3 warm-up + 5 timed batch-2 steps, fewer when the budget runs out (what ran is stated); (3) one batch-16 step if the
-    measured batch-2 rate says it fits 30 s.  `reference_in_build_container`: the IMPORTED reference's own train_gan at the same
+    (capped at the host's cores, and at OMP_NUM_THREADS when set) on a generator-only forward, stopped at the first count that
+    is slower than the best (torch-CPU oversubscribes a 256-core host: on the round-6 box 16 threads 3.7 s, 64 5.3 s, 128 10.1 s
+    -- the sweep says so in two forwards instead of spending the budget proving it); (2) at the best count: 3 warm-up + 5 timed
+    batch-2 steps, fewer when the budget runs out (what ran is stated); (3) one batch-16 step if the measured batch-2 rate says it
+    fits 30 s.  `reference_in_build_container`: the IMPORTED reference's own train_gan at the same
     protocol, measured in the build container (tools/time_reference_cpu.py; the reference cannot travel to this box)."""
     from oracle import se_oracle as Or
     import formula
     ncpu = os.cpu_count() or 1
+    cap = min(ncpu, int(os.environ.get('OMP_NUM_THREADS') or ncpu))     # the process's thread allowance, when one is set
     gsd = formula.formula_state('generator')
     clean, noisy, _ = synth_batch(2, 32000, 1, 'cpu')
     cn, nn_, _c = Or.normalize_pair(clean, noisy)
@@ -112,11 +115,11 @@ def cpu_baseline(budget_s=48.0):
     sweep = {}
     t_start = time.time()
     best = None
-    torch.set_num_threads(min(ncpu, 16))
+    torch.set_num_threads(min(cap, 16))
     with torch.no_grad():
         Or.tscnet_forward(gsd, spec, False)                  # warm once (allocator, thread pool)
     stop = False
-    for th in sorted({min(ncpu, v) for v in (16, 32, 64, 128)}):
+    for th in sorted({min(cap, v) for v in (16, 32, 64, 128)}):
         if stop:
             sweep[th] = None                                 # skipped: an earlier count was already slower than the best
             continue
@@ -340,6 +343,23 @@ def secondary_configs(G, D, og, od, dev, budget_s=25.0):
     return res
 
 
+def dump_outputs(path, out, models, optimizers):
+    """what the caller of the train step holds after its last call, as <path>/<name>.npy: every loss term (float64 scalar), the
+    parameters after the optimizer updates (the optimizers' flat fp32 buffers) and the floating-point buffers of each model
+    (BatchNorm running statistics, spectral-norm vectors); 8 MB in all at the default size"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        if hasattr(v, 'item') or isinstance(v, float):
+            np.save(os.path.join(path, f'{k}.npy'), np.array(float(v), dtype=np.float64))
+    for name, m, o in zip(('generator', 'discriminator'), models, optimizers):
+        params = torch.cat([g['flat'].reshape(-1) for g in o.param_groups])
+        bufs = [b.detach().reshape(-1).float() for b in m.buffers() if b.dtype.is_floating_point]
+        np.save(os.path.join(path, f'{name}_params.npy'), params.float().cpu().numpy())
+        if bufs:
+            np.save(os.path.join(path, f'{name}_buffers.npy'), torch.cat(bufs).cpu().numpy())
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` without a launcher: start N ranks with torch.distributed.run as a CHILD process -- decided
     before anything in this process touches the GPU -- and hand its exit code back.  Rank 0 of the children prints the
@@ -363,7 +383,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--batch', type=int, default=16, help='utterances per GPU per step')
     ap.add_argument('--arch', default='cmgan')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the CPU baseline, clocks, per-kernel roofline and secondary configurations (extra runs)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the losses and the updated parameters of the last timed step as DIR/<name>.npy')
     a = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
@@ -376,7 +400,7 @@ def main():
         sys.exit(f'bench.py: --gpus {a.gpus} does not match WORLD_SIZE={world} set by the launcher')
     # The CPU-baseline leg needs no GPU: it runs FIRST (rank 0, N = 1 only), bounded to ~30-40 s, so that the GPU section of the
     # command is contiguous and not a sliver at the start of a CPU-dominated run.
-    cpu_res = cpu_baseline() if (world == 1 and not a.no_cpu_baseline) else None
+    cpu_res = cpu_baseline() if (a.full and world == 1 and not a.no_cpu_baseline) else None
     torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -431,17 +455,31 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
-    # shader clock / board power under the same load: a SEPARATE untimed pass of the same steps right after the timed region (the
-    # sampler's sysfs reads issue SMU queries and take the GIL on rank 0 only: they do not belong inside a max-over-ranks timing)
-    clock_res = None
+    # the results of the last timed step are read here, before any further step (--full) changes the models
     if rank == 0:
-        clocks = ClockSampler(local)
-        clocks.start()
-    for _ in range(min(a.steps, 10)):
-        step()
-    fence()
-    if rank == 0:
-        clock_res = clocks.stop()
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out, (G, D), (og, od))
+        bad = [k for k, v in out.items() if hasattr(v, 'item') and not torch.isfinite(v).all()]
+        if bad:
+            sys.exit(f'bench.py: non-finite loss terms after the timed steps: {bad}')
+    res = {
+        'metric': 'utterances/sec (2 s @16 kHz) CMGAN train step', 'value': round(world * B * a.steps / dt, 3),
+        'unit': 'utterances/sec', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
+        'ms_per_step': round(dt / a.steps * 1e3, 2), 'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': 'f32 (f16x3 split)', 'data': 'synthetic',
+        'config': {'workload': f'{a.arch} generator+discriminator train step (main_gan.py train_gan loop body), '
+                               f'batch {B}/GPU, 2 s @ 16 kHz, n_fft=400 hop=100, AdamW lr 5e-4, PESQ labels supplied, '
+                               f'kaiming-init weights; fp32 results throughout: conv and token GEMMs as scaled fp16 hi/lo splits '
+                               f'(3 MFMAs per product, 2^-24 relative, fp32 accumulate), attention on the same scaled fp16 splits (scales from measured operand maxima), '
+                               f'everything else fp32 MFMA / fp32 VALU',
+                   'global_batch': world * B, 'parallelism': f'dp{world}',
+                   'effective_tflops': round(world * B * a.steps * GFLOP_PER_UTT_STEP / dt / 1e3, 2),
+                   'dropout': 'generator ff/attn dropout p=0.2 on (counter-based masks in the GEMM pro/epilogues); '
+                              'discriminator Dropout(0.3) on'},
+        'losses': {k: round(float(v), 5) for k, v in out.items() if hasattr(v, 'item') or isinstance(v, float)},
+    }
+    res['dtype_note'] = ('results and accumulators fp32; MFMA-bound products evaluated as 3 fp16 MFMAs on scaled (hi, lo) fp16 operand '
+                         'splits (fp32-equivalent: measured against fp64 at or below the fp32-MFMA kernels\' error, tests/test_f16x3_gpu.py)')
     # self-validation of the data-parallel run (every rank; the first N > 1 run on hardware must prove itself): after W + K steps all
     # ranks must hold bit-identical parameters and BatchNorm running statistics -- identical initial broadcast, identical averaged
     # gradients, deterministic kernels.  A mismatch fails the run instead of printing a throughput for diverged replicas.
@@ -467,6 +505,24 @@ def main():
             bad_ranks = [int(allid[i][0]) for i, c in enumerate(allcs) if not bool((c == allcs[0]).all())]
             sys.exit(f'bench.py: data-parallel replicas DIVERGED after {a.warmup + a.steps} steps: ranks {bad_ranks} differ from rank 0 '
                      f'(state checksums) -- the throughput of diverged replicas is not a result')
+        res['data_parallel_check'] = dp_check
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(res))
+        if world > 1 or force_dp:
+            dist.destroy_process_group()
+        return
+    # shader clock / board power under the same load: a SEPARATE untimed pass of the same steps right after the timed region (the
+    # sampler's sysfs reads issue SMU queries and take the GIL on rank 0 only: they do not belong inside a max-over-ranks timing)
+    clock_res = None
+    if rank == 0:
+        clocks = ClockSampler(local)
+        clocks.start()
+    for _ in range(min(a.steps, 10)):
+        step()
+    fence()
+    if rank == 0:
+        clock_res = clocks.stop()
     # attribution pass 1 (all ranks: the step contains collectives): 2 more steps in the SAME concurrent stream order with two HIP
     # events around every keyed launch and, for N > 1, around the data-parallel exchanges (`comm`)
     conc_steps = 2
@@ -494,9 +550,6 @@ def main():
             dist.destroy_process_group()
         return
 
-    bad = [k for k, v in out.items() if hasattr(v, 'item') and not torch.isfinite(v).all()]
-    if bad:
-        sys.exit(f'bench.py: non-finite loss terms after the timed steps: {bad}')
     conc = _lib.TIMER.summary()          # concurrent-order pass: weight-gradient and discriminator streams on -> launches overlap
     # Per-kernel attribution: with the streams on a launch's elapsed time is not the kernel's own (kernels of three streams share
     # the machine).  The roofline object is therefore measured on 2 extra steps in SERIAL stream order right after the timed
@@ -626,31 +679,10 @@ def main():
                                              '(2 FETCH_SIZE + WRITE_SIZE over all launches), from the committed PMC passes')
         roof['peak_note'] = ('peak = the 2.4 GHz dense figure of MI355X_MICROARCH.md; with the matrix pipe kept full this part sustains 1.13 - 1.18 GHz '
                              '(vector-only streams 1.52 GHz): profiles/r06_clock_density.txt, tools/micro/clock_density.hip')
-    a = argparse.Namespace(**{**vars(a), 'steps': a_steps})
-    res = {
-        'metric': 'utterances/sec (2 s @16 kHz) CMGAN train step', 'value': round(world * B * a.steps / dt, 3),
-        'unit': 'utterances/sec', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
-        'ms_per_step': round(dt / a.steps * 1e3, 2), 'higher_is_better': True, 'scaling': 'weak',
-        'vs_baseline': None, 'dtype': 'f32 (f16x3 split)', 'data': 'synthetic',
-        'config': {'workload': f'{a.arch} generator+discriminator train step (main_gan.py train_gan loop body), '
-                               f'batch {B}/GPU, 2 s @ 16 kHz, n_fft=400 hop=100, AdamW lr 5e-4, PESQ labels supplied, '
-                               f'kaiming-init weights; fp32 results throughout: conv and token GEMMs as scaled fp16 hi/lo splits '
-                               f'(3 MFMAs per product, 2^-24 relative, fp32 accumulate), attention on the same scaled fp16 splits (scales from measured operand maxima), '
-                               f'everything else fp32 MFMA / fp32 VALU',
-                   'global_batch': world * B, 'parallelism': f'dp{world}',
-                   'effective_tflops': round(world * B * a.steps * GFLOP_PER_UTT_STEP / dt / 1e3, 2),
-                   'dropout': 'generator ff/attn dropout p=0.2 on (counter-based masks in the GEMM pro/epilogues); '
-                              'discriminator Dropout(0.3) on'},
-        'losses': {k: round(float(v), 5) for k, v in out.items() if hasattr(v, 'item') or isinstance(v, float)},
-        'roofline': roof,
-    }
-    res['dtype_note'] = ('results and accumulators fp32; MFMA-bound products evaluated as 3 fp16 MFMAs on scaled (hi, lo) fp16 operand '
-                         'splits (fp32-equivalent: measured against fp64 at or below the fp32-MFMA kernels\' error, tests/test_f16x3_gpu.py)')
+    res['roofline'] = roof
     res['clocks'] = clock_res
     if comm is not None:
         res['comm'] = comm
-    if dp_check is not None:
-        res['data_parallel_check'] = dp_check
     if world == 1 and not force_dp and os.environ.get('SE_BENCH_NO_SECONDARY') != '1' and a.arch == 'cmgan' and a.batch == 16:
         res['secondary'] = secondary_configs(G, D, og, od, dev)
     if cpu_res is not None:

@@ -1,15 +1,17 @@
 #!/bin/bash
 # same-box A/B of the product library against a variant library (tools/build_variant_lib.sh): tools/fam_ab.sh <variant .so> [rounds]
-# -> per family ms per step of both, from bench.py's serial-order attribution pass (headline loop only, no CPU leg)
-lib=$1; rounds=${2:-2}
+# [out dir] -> per family ms per step of both, from the serial-order attribution pass of bench.py --full (no CPU leg); the JSON
+# lines go to <out dir> (default: bench_out)
+lib=$1; rounds=${2:-2}; out=${3:-bench_out}
+mkdir -p $out
 for k in $(seq 1 $rounds); do
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/fam_${k}_prod.json 2> gpurun_out/fam_${k}_prod.err
-  SE_HIP_LIB=$lib python bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/fam_${k}_var.json 2> gpurun_out/fam_${k}_var.err
+  python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $out/fam_${k}_prod.json 2> $out/fam_${k}_prod.err
+  SE_HIP_LIB=$lib python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $out/fam_${k}_var.json 2> $out/fam_${k}_var.err
 done
-python - <<'P'
-import json,glob
+python - "$out" <<'P'
+import json,glob,sys
 r={}
-for f in sorted(glob.glob('gpurun_out/fam_*_*.json')):
+for f in sorted(glob.glob(sys.argv[1] + '/fam_*_*.json')):
     d=json.load(open(f)); w=f.split('_')[-1][:-5]
     r.setdefault(w,[]).append(d)
 fams=list(r['prod'][0]['roofline']['families'].keys())
