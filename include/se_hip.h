@@ -388,6 +388,16 @@ int se_dwconv31_bwd_fused(const float* dH, const float* W, const float* U, const
                           long pos_stride, void* stream);
 int se_dwconv31_wgrad(const float* X, const float* dY, float* dW, float* dbias, int nseq, int n, int inner,
                       long outer_stride, long inner_stride, long pos_stride, float* ws, void* stream);
+/* The same sweep with the train-mode BatchNorm1d + Swish backward of the Conformer conv module in front of it (conformer.py:164-169
+ * backwards) applied while the rows are staged: dH = rstd gamma (du - m1 - xh m2), du = dY swish'(xh gamma + beta), xh = (H - mean) rstd,
+ * m1 = red[c][0] / count, m2 = red[c][1] / count -- se_norm_prelu_bwd's apply pass (act = 1, one statistics row), whose dH never goes to
+ * memory here.  dY = the gradient of the Swish output [ntok][128], H = the BatchNorm input, mr = (mean, rstd) [128][2], gamma / beta [128],
+ * red = the table of se_norm_prelu_bwd's reduce pass (phase 1; all-reduced by a data-parallel caller), count = tokens behind it;
+ * dgamma / dbeta (may be NULL) += red[c][1] / red[c][0] (phase 8 of that entry point).  The other operands as in se_dwconv31_bwd_fused. */
+int se_dwconv31_bn_bwd_fused(const float* dY, const float* H, const float* mr, const float* gamma, const float* beta, const double* red,
+                             double count, float* dgamma, float* dbeta, const float* W, const float* U, const float* G, float* dZ,
+                             float* amax_out, float* dW, float* dbias, float* ws, long ntok, int nseq, int n, int inner,
+                             long outer_stride, long inner_stride, long pos_stride, void* stream);
 
 /* ---- front-end glue, output assembly, losses, optimizers (csrc/se_elem.hip) --------------------- */
 /* normalize_batch (core/function.py:647-659): c[b] = sqrt(L / sum x^2) */

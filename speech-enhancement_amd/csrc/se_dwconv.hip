@@ -372,6 +372,10 @@ struct DwBwdArgs {
   SeqGeom g;
   const float* dH; const float* W; const float* U; const float* Z; float* dZ; float* amax_out; float* part;
   unsigned bytes128, bytes256;      // extents of the [tokens][128] operands and of dZ [tokens][256]
+  // BatchNorm form (dwconv_bwd_fused_kernel_bn, se_dwconv31_bn_bwd_fused): dH = dY (the Swish output's gradient), X = h, mr = (mean,
+  // rstd) [128][2], gamma / beta [128], red = the reduce pass's (sum du, sum du xh, .) [128][3], count = tokens behind the statistics,
+  // dgamma / dbeta (may be NULL): += the sums
+  const float* X; const float* mr; const float* gamma; const float* beta; const double* red; double count; float* dgamma; float* dbeta;
 };
 constexpr int FB_PPS = 7, FB_TILE = 16 * FB_PPS, FB_ROWS = FB_TILE + DW_K - 1, FB_NLD = (FB_ROWS * 32 + 1023) / 1024,
               FB_NLU = (FB_TILE * 32 + 1023) / 1024;
@@ -379,13 +383,28 @@ typedef unsigned u32x2fb_ __attribute__((ext_vector_type(2)));
 #ifndef FB_NT
 #define FB_NT 8                         // taps per wave in the weight-gradient phase (4: twice the LDS reads; 8: +8 persistent VGPRs)
 #endif
+#ifndef FB_NT_BN
+#define FB_NT_BN 4                      // the same in the BatchNorm form: its h ring (20 VGPRs) is live across phase B -- with 8 taps per
+#endif                                  // wave it spills (128 VGPRs + 116 B of scratch), with 4: 126 VGPRs, no scratch, 4 waves per SIMD
 constexpr int FB_LDS_BYTES = (FB_ROWS * DW_C + FB_TILE * DW_C + DW_K * DW_C) * 4;
+constexpr int FB_LDS_BYTES_BN = FB_LDS_BYTES + 7 * DW_C * 4;       // + the BatchNorm constants [7][128]
 
-__global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) {
+// BN (dwconv_bwd_fused_kernel_bn): the apply pass of the train-mode BatchNorm + Swish backward (norm_prelu_bwd_apply_kernel, act = 1:
+// the same arithmetic in the same order) is done on the rows on their way into LDS -- du = dY swish'(xh gamma + beta), dH = rstd gamma
+// (du - m1 - xh m2), xh = (h - mean) rstd -- from the dY rows and the h rows of the tile window (both requested one tile ahead; padding
+// rows stay zero).  The statistics m1, m2 come from norm_prelu_bwd_reduce_kernel's table, so dH is what the two-pass form stores.
+// Register budget: the h ring (5 float4) is live across phase B next to the dY and U rings; phase B then takes 4 taps per wave instead
+// of 8 (FB_NT_BN: 8 fewer persistent accumulators and 8 fewer row registers, for twice phase B's LDS reads) -- 4 waves per SIMD, no
+// scratch, the full one-tile-ahead prefetch of both streams.  Not taken: a direct-to-LDS h window (a second 71 KB window does not fit
+// next to the 146 KB in use) and a shallower h prefetch (one exposed memory round trip per tile in a one-workgroup-per-CU kernel).
+// The per-channel constants come from LDS, computed once per workgroup.
+template <bool BN>
+static __device__ __forceinline__ void dwconv_bwd_fused_body(const DwBwdArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float fb_smem[];
   float* xs = fb_smem;                          // [142][128]: dH rows p0 - 15 .. p0 + 126
   float* us = fb_smem + FB_ROWS * DW_C;         // [112][128]: U rows p0 .. p0 + 111
   float* wt = us + FB_TILE * DW_C;              // [31][128]: taps in input-gradient (flipped) order
+  float* bnt = wt + DW_K * DW_C;                // BN: [mean | rstd | rstd gamma | m1 | m2 | gamma | beta][128]
   const int tid = threadIdx.x, cl = tid & 63, ps = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned cl8 = (unsigned)cl * 8u;
   const int n = a.g.n;
@@ -393,15 +412,32 @@ __global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) {
     const int ch = i / DW_K, k = i - ch * DW_K;
     wt[(DW_K - 1 - k) * DW_C + ch] = a.W[i];
   }
+  if constexpr (BN) {
+    if (tid < DW_C) {                           // the two fp64 divisions once per channel (ordered by the tile loop's first barrier)
+      const int c = tid;
+      const float mean = a.mr[2 * c], rstd = a.mr[2 * c + 1];
+      bnt[c] = mean;
+      bnt[DW_C + c] = rstd;
+      bnt[2 * DW_C + c] = rstd * a.gamma[c];
+      bnt[3 * DW_C + c] = (float)(a.red[c * 3] / a.count);
+      bnt[4 * DW_C + c] = (float)(a.red[c * 3 + 1] / a.count);
+      bnt[5 * DW_C + c] = a.gamma[c];
+      bnt[6 * DW_C + c] = a.beta[c];
+      if (a.dgamma && blockIdx.x == 0) {         // norm_prelu_bwd_apply_kernel's parameter gradients (one statistics row)
+        a.dgamma[c] += (float)a.red[c * 3 + 1];
+        a.dbeta[c] += (float)a.red[c * 3];
+      }
+    }
+  }
   const __amdgpu_buffer_rsrc_t rH = make_rsrc_(a.dH, a.bytes128), rU = make_rsrc_(a.U, a.bytes128), rG = make_rsrc_(a.Z, a.bytes128),
-                               rD = make_rsrc_(a.dZ, a.bytes256);
+                               rD = make_rsrc_(a.dZ, a.bytes256), rX = make_rsrc_(BN ? a.X : a.dH, a.bytes128);
   const int tiles = (n + FB_TILE - 1) / FB_TILE;
   const long nitems = (long)a.g.nseq * tiles;
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, S = gridDim.x >> 3;
   const long Q = (nitems + 7) >> 3, ibase = (long)xcd * Q, iend = ibase + Q < nitems ? ibase + Q : nitems;
   const unsigned rsb = (unsigned)(a.g.pos_stride * DW_C * 4);          // bytes between consecutive positions of a sequence
   float zmax = 0.f;
-  float4 ld[FB_NLD], lu[FB_NLU];
+  float4 ld[FB_NLD], lu[FB_NLU], lh[BN ? FB_NLD : 1];
   // rows of item `it` (all-zero rows for it >= iend): dH row r = (tid >> 5) + 32 k <-> position p0 - 15 + r, U row r <-> p0 + r.
   // Offsets = a wave-uniform part per load + ONE lane constant (mod 2^32: rows above the sequence wrap and are deselected)
   const int lrow = tid >> 5;
@@ -420,6 +456,7 @@ __global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) {
       const int row = lrow + 32 * k;
       const unsigned off = base + (unsigned)(p0 - 15 + 32 * k) * rsb + lane_off;
       ld[k] = buf_load4_(rH, (unsigned)(row - plo) < span ? off : BUF_OOB_);
+      if constexpr (BN) lh[BN ? k : 0] = buf_load4_(rX, (unsigned)(row - plo) < span ? off : BUF_OOB_);
     }
 #pragma unroll
     for (int k = 0; k < FB_NLU; ++k) {
@@ -429,7 +466,7 @@ __global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) {
     }
   };
   // phase-B role of this wave: taps 4 tg .. 4 tg + 3 (k = 31: bias gradient), positions 56 ph .. 56 ph + 55 of the tile
-  constexpr int NT = FB_NT, NGRP = 32 / NT, NPART = 16 / NGRP, PLEN = FB_TILE / NPART;      // taps per wave, tap groups, position parts
+  constexpr int NT = BN ? FB_NT_BN : FB_NT, NGRP = 32 / NT, NPART = 16 / NGRP, PLEN = FB_TILE / NPART;      // taps per wave, tap groups, position parts
   const int tg = ps % NGRP, ph = ps / NGRP;
   f32x2 wacc[NT];
 #pragma unroll
@@ -439,15 +476,50 @@ __global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) {
     const int seq = (int)(it / tiles), p0 = (int)(it - (long)seq * tiles) * FB_TILE;
     const unsigned base = (unsigned)(((long)(seq / a.g.inner) * a.g.outer_stride + (long)(seq % a.g.inner) * a.g.inner_stride) * (DW_C * 4));
     __syncthreads();                           // previous tile's LDS reads (phase B) done; first pass: tap table written
+    if constexpr (BN) {
+      // U rows first (their ring is dead before the transform); then channel by channel (7 constants live at a time, not 28), in place
 #pragma unroll
-    for (int k = 0; k < FB_NLD; ++k) {
-      const int row = lrow + 32 * k;
-      if (row < FB_ROWS) *reinterpret_cast<float4*>(&xs[row * DW_C + (tid & 31) * 4]) = ld[k];
+      for (int k = 0; k < FB_NLU; ++k) {
+        const int row = lrow + 32 * k;
+        if (row < FB_TILE) *reinterpret_cast<float4*>(&us[row * DW_C + (tid & 31) * 4]) = lu[k];
+      }
+      const int c4 = (tid & 31) * 4;
+      const int plo = 15 - p0 > 0 ? 15 - p0 : 0;        // the window rows that are real positions (as in request_rows)
+      const int phi = n - (p0 - 15) < FB_ROWS ? n - (p0 - 15) : FB_ROWS;
+      const unsigned span = phi > plo ? (unsigned)(phi - plo) : 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float mean = bnt[c4 + j], rstd = bnt[DW_C + c4 + j], ag = bnt[2 * DW_C + c4 + j], m1 = bnt[3 * DW_C + c4 + j];
+        const float m2 = bnt[4 * DW_C + c4 + j], gg = bnt[5 * DW_C + c4 + j], bt = bnt[6 * DW_C + c4 + j];
+#pragma unroll
+        for (int k = 0; k < FB_NLD; ++k) {
+          const bool real = (unsigned)(lrow + 32 * k - plo) < span;
+          float& d = j == 0 ? ld[k].x : (j == 1 ? ld[k].y : (j == 2 ? ld[k].z : ld[k].w));
+          const float h = j == 0 ? lh[k].x : (j == 1 ? lh[k].y : (j == 2 ? lh[k].z : lh[k].w));
+          const float xh = (h - mean) * rstd;
+          const float u = xh * gg + bt;
+          const float du = d * swish_gradf_(u);
+          d = real ? ag * (du - m1 - xh * m2) : 0.f;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < FB_NLD; ++k) {
+        const int row = lrow + 32 * k;
+        if (row < FB_ROWS) *reinterpret_cast<float4*>(&xs[row * DW_C + c4]) = ld[k];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < FB_NLD; ++k) {
+        const int row = lrow + 32 * k;
+        if (row < FB_ROWS) *reinterpret_cast<float4*>(&xs[row * DW_C + (tid & 31) * 4]) = ld[k];
+      }
     }
+    if constexpr (!BN) {
 #pragma unroll
-    for (int k = 0; k < FB_NLU; ++k) {
-      const int row = lrow + 32 * k;
-      if (row < FB_TILE) *reinterpret_cast<float4*>(&us[row * DW_C + (tid & 31) * 4]) = lu[k];
+      for (int k = 0; k < FB_NLU; ++k) {
+        const int row = lrow + 32 * k;
+        if (row < FB_TILE) *reinterpret_cast<float4*>(&us[row * DW_C + (tid & 31) * 4]) = lu[k];
+      }
     }
     __syncthreads();
     // gate values of the own positions: requested ahead of the FIR that hides their latency
@@ -593,6 +665,9 @@ __global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) {
   *reinterpret_cast<float4*>(prow + t2 * 4) = t;
 }
 
+__global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel(DwBwdArgs a) { dwconv_bwd_fused_body<false>(a); }
+__global__ __launch_bounds__(1024) void dwconv_bwd_fused_kernel_bn(DwBwdArgs a) { dwconv_bwd_fused_body<true>(a); }
+
 extern "C" int se_dwconv31(const float* X, const float* W, const float* bias, float* Y, double* stats, int flip,
                            int nseq, int n, int inner, long outer_stride, long inner_stride, long pos_stride,
                            void* stream) {
@@ -674,4 +749,29 @@ extern "C" int se_dwconv31_bwd_fused(const float* dH, const float* W, const floa
   hipLaunchKernelGGL(dwconv_wgrad_reduce_kernel, dim3(32 * DW_C / 256, 32), dim3(256), 0, as_stream(stream), (const float*)ws, nblk,
                      dW, dbias);
   return se_check_launch("se_dwconv31_bwd_fused");
+}
+
+// the same sweep with the BatchNorm + Swish apply pass done while the rows are staged (dwconv_bwd_fused_kernel_bn): dY = the gradient of
+// the Swish output, H = the BatchNorm input, red = norm_prelu_bwd's reduce table (all-reduced by a data-parallel caller)
+extern "C" int se_dwconv31_bn_bwd_fused(const float* dY, const float* H, const float* mr, const float* gamma, const float* beta, const double* red,
+                                        double count, float* dgamma, float* dbeta, const float* W, const float* U, const float* G, float* dZ,
+                                        float* amax_out, float* dW, float* dbias, float* ws, long ntok, int nseq, int n, int inner,
+                                        long outer_stride, long inner_stride, long pos_stride, void* stream) {
+  SE_REQUIRE(dY && H && mr && gamma && beta && red && count > 0 && (!dgamma == !dbeta) && W && U && G && dZ && dW && ws && nseq > 0 && n > 0 &&
+             inner > 0 && ntok > 0, "dwconv31_bn_bwd_fused: bad arguments");
+  SE_REQUIRE(ntok * (DW_C * 8L) < (1L << 32) - 4096, "dwconv31_bn_bwd_fused: operands beyond 32-bit buffer offsets (%ld tokens)", ntok);
+  SE_REQUIRE(pos_stride > 0 && (long)(nseq - 1) / inner * outer_stride + (long)(inner - 1) * inner_stride + (long)(n - 1) * pos_stride < ntok,
+             "dwconv31_bn_bwd_fused: sequence geometry reaches past %ld tokens", ntok);
+  DwBwdArgs a{{nseq, n, inner, outer_stride, inner_stride, pos_stride}, dY, W, U, G, dZ, amax_out, ws,
+              (unsigned)(ntok * DW_C * 4), (unsigned)(ntok * DW_C * 8), H, mr, gamma, beta, red, count, dgamma, dbeta};
+  const long nitems = (long)nseq * cdiv(n, FB_TILE);
+  const int ncu = se_cu_count();
+  int nblk = nitems < ncu ? (int)((nitems + 7) / 8 * 8) : ncu / 8 * 8;
+  if (nblk > 512) nblk = 512;
+  static unsigned lds_done = 0;
+  SE_REQUIRE(se_raise_lds((const void*)dwconv_bwd_fused_kernel_bn, FB_LDS_BYTES_BN, &lds_done), "dwconv31_bn_bwd_fused: cannot raise the LDS limit");
+  hipLaunchKernelGGL(dwconv_bwd_fused_kernel_bn, dim3(nblk), dim3(1024), FB_LDS_BYTES_BN, as_stream(stream), a);
+  hipLaunchKernelGGL(dwconv_wgrad_reduce_kernel, dim3(32 * DW_C / 256, 32), dim3(256), 0, as_stream(stream), (const float*)ws, nblk,
+                     dW, dbias);
+  return se_check_launch("se_dwconv31_bn_bwd_fused");
 }

@@ -61,6 +61,10 @@ FUSE_LN_BWD = True
 FUSE_ROWSTATS = True
 # GLU backward in the epilogue of the depthwise input-gradient kernel (se_dwconv31_glu_bwd)
 FUSE_GLU_BWD = True
+# train-mode BatchNorm + Swish backward of the conv module: the apply pass done by the fused depthwise backward while it stages its rows
+# (round 7; dH never goes to memory, the reduce pass is unchanged).  False: the two norm_prelu_bwd passes (fallback outside the guards,
+# cross-check of the tests)
+FUSE_BN_BWD = True
 
 
 def set_conv_precision(name, wgrad=None):
@@ -667,17 +671,24 @@ def conformer_bwd(P, G, p, ctx, dout, B, T, Fq, dp=NO_DP, train=True):
                                          **_bnd(P, ('bn', f'{p}.conv'), GM.HID_SEXP, need_k1=max(count - 1.0, 1.0) ** 0.5),
                                          w_amax=getattr(dy3, '_se_amax', None)), h, dy3,
                           G[f'{p}.conv.net.7.weight'].view(64, 128), G[f'{p}.conv.net.7.bias'], ps=sc, pb=sh)
-    dh = torch.empty(M, 128, device=dev, dtype=torch.float32)
     g_bn, b_bn = P[f'{p}.conv.net.5.weight'], P[f'{p}.conv.net.5.bias']
-    if train:
-        O.norm_prelu_bwd(h, 128, 0, mr, g_bn, b_bn, None, dact, 128, 0, dh, 128, 0, G[f'{p}.conv.net.5.weight'],
-                         G[f'{p}.conv.net.5.bias'], None, 1, M, 128, per_batch=False, act=1,
-                         allreduce=(dp.allreduce if dp.world > 1 or getattr(dp, 'force_sync', False) else None), count=count)
-    else:
-        raise L.SeHipError('conformer_bwd in eval mode is not supported (BatchNorm uses running statistics)')
     Wdw = P[f'{p}.conv.net.4.conv.weight'].view(128, 31)
     dw_fused = FUSE_GLU_BWD and O.DW_BWD_FUSED and M * 1024 < (1 << 32) - 4096
-    if dw_fused:           # ... and the weight / bias gradient from the rows the same kernel already holds (round 5)
+    allreduce = dp.allreduce if dp.world > 1 or getattr(dp, 'force_sync', False) else None
+    bn_fold = FUSE_BN_BWD and dw_fused
+    if not bn_fold:
+        dh = torch.empty(M, 128, device=dev, dtype=torch.float32)
+        O.norm_prelu_bwd(h, 128, 0, mr, g_bn, b_bn, None, dact, 128, 0, dh, 128, 0, G[f'{p}.conv.net.5.weight'],
+                         G[f'{p}.conv.net.5.bias'], None, 1, M, 128, per_batch=False, act=1, allreduce=allreduce, count=count)
+    if bn_fold:
+        # the reduce pass as before; its apply pass inside the depthwise sweep (the parameter gradients there too, unless the local sums
+        # were taken before the cross-rank exchange): dH never goes to memory
+        red = O.bn_swish_bwd_sums(h, mr, g_bn, b_bn, dact, G[f'{p}.conv.net.5.weight'], G[f'{p}.conv.net.5.bias'], count, allreduce=allreduce)
+        dzc = O.dwconv31_bn_bwd_fused(dact, h, mr, g_bn, b_bn, red, count, Wdw, u, zc, G[f'{p}.conv.net.4.conv.weight'].view(128, 31),
+                                      G[f'{p}.conv.net.4.conv.bias'], geom, amax=_amax(dev),
+                                      **({} if allreduce is not None else dict(dg=G[f'{p}.conv.net.5.weight'], dbeta=G[f'{p}.conv.net.5.bias'])))
+        dh = du = None
+    elif dw_fused:         # ... and the weight / bias gradient from the rows the same kernel already holds (round 5)
         dzc = O.dwconv31_bwd_fused(dh, Wdw, u, zc, G[f'{p}.conv.net.4.conv.weight'].view(128, 31), G[f'{p}.conv.net.4.conv.bias'], geom,
                                    amax=_amax(dev))
         du = None

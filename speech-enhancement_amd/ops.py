@@ -199,6 +199,37 @@ def dwconv31_bwd_fused(dh, w, u, gate, dw, dbias, geom, amax=None):
     return dz
 
 
+def bn_swish_bwd_sums(h, mr, g, beta, dy, dg, dbeta, count, allreduce=None):
+    """the reduce pass of norm_prelu_bwd for the train-mode BatchNorm1d(128) + Swish of the Conformer conv module (act = 1, one statistics
+    row): returns red [1][128][3] (sum du, sum du xh, 0).  allreduce (SyncBatchNorm): dg / dbeta += the LOCAL sums here (phase 4), then
+    red is all-reduced; without it dwconv31_bn_bwd_fused adds them (the apply pass's phase 8)."""
+    M = h.shape[0]
+    red = zeros(L.lib().se_norm_prelu_bwd_workspace_bytes(_i(1), _i(128), _i(0)) // 8, device=h.device, dtype=f64)
+    # phase 1 (| 4): the apply pass is the depthwise kernel's -- dX is not written (dy stands in for the pointer the entry point checks)
+    L.call('se_norm_prelu_bwd_amax', L.ptr(h), _i(128), _i(0), L.ptr(mr), L.ptr(g), L.ptr(beta), L.ptr(None), L.ptr(dy), _i(128), _i(0),
+           L.ptr(red), L.ptr(dy), _i(128), _i(0), L.ptr(dg), L.ptr(dbeta), L.ptr(None), _i(1), _l(M), _i(128), _i(0), _i(1),
+           _i(1 | 16 | (4 if allreduce is not None else 0)), _d(count), L.ptr(None), L.stream())
+    if allreduce is not None:
+        allreduce(red)
+    return red
+
+
+def dwconv31_bn_bwd_fused(dy, h, mr, gamma, beta, red, count, w, u, gate, dw, dbias, geom, dg=None, dbeta=None, amax=None):
+    """dwconv31_bwd_fused on dH = the train-mode BatchNorm + Swish backward of dy (the apply pass of norm_prelu_bwd with red from
+    bn_swish_bwd_sums; count: tokens behind the statistics), done while the kernel stages its rows: dH never goes to memory.
+    dg / dbeta (optional): += the sums of red (pass them only when bn_swish_bwd_sums did not)"""
+    M = dy.shape[0]
+    dz = torch.empty(M, 256, device=dy.device, dtype=torch.float32)
+    nseq, n, inner, os_, is_, ps = geom
+    ws = _new(L.lib().se_dwconv31_wgrad_workspace_bytes() // 4, like=dy)
+    L.call('se_dwconv31_bn_bwd_fused', L.ptr(dy), L.ptr(h), L.ptr(mr), L.ptr(gamma), L.ptr(beta), L.ptr(red), _d(count), L.ptr(dg),
+           L.ptr(dbeta), L.ptr(w), L.ptr(u), L.ptr(gate), L.ptr(dz), L.ptr(amax), L.ptr(dw), L.ptr(dbias), L.ptr(ws), _l(M), _i(nseq),
+           _i(n), _i(inner), _l(os_), _l(is_), _l(ps), L.stream(), _key='dwconv31 bn_bwd + dgrad + glu_bwd + wgrad',
+           _bytes=4.0 * (4 * dy.numel() + dz.numel()))
+    dz._se_amax = amax
+    return dz
+
+
 def dwconv31_wgrad(x, dy, dw, dbias, geom):
     nseq, n, inner, os_, is_, ps = geom
     ws = _new(L.lib().se_dwconv31_wgrad_workspace_bytes() // 4, like=x)
