@@ -549,6 +549,30 @@ int se_group_finalize(const double* stats, int B, int Ntot, int c_off, int N, in
 /* out[pos] = b + sum_c relu(h[pos][c]) w[c]   (:159-161) */
 int se_diff_out(const float* h, const float* w, const float* bias, float* out, long npos, int C, void* stream);
 
+/* ---- objective metrics (utils/compute_metrics.py: WSS, LLR, segmental SNR, STOI), fp64 on the device ----
+ * A batch is B utterances of different lengths: the clean and the processed signals are packed alike into one flat fp32 buffer
+ * each, and `meta` (device, int64 [B][SE_METRIC_META]) describes utterance b:
+ *   0 sample offset   1 length L                    2 offset of its frame measures   3 frames  int(L / 120 - 4)
+ *   4 offset of its resampled signal   5 its length ceil(5 L / 8) = n   6 offset of its STOI frames   7 their number ceil((n - 256) / 128)
+ *   8 promote: 1 = the reference promoted the pair to fp64 and added 2^-52 (compute_metrics with unequal lengths), 0 = float32 input
+ * Constant tables (device, fp64, made by the host once): window [480] 0.5 (1 - cos(2 pi k / 481)), k = 1..480; twiddle [512][2]
+ * (cos, -sin)(2 pi k / 1024); crit_filter [25][512]; fir [2][161] resampling taps (row 0 rounded to float32, row 1 fp64);
+ * hann [256] = hann(258)[1:257]; thirdoct [15][257]. */
+#define SE_METRIC_META 9
+/* per-frame WSS, LLR, segmental SNR (clamped to [-10, 35]) -> wss / llr / snr [sum of frames]; max_frames = largest frame count */
+int se_metric_frames(const float* clean, const float* enh, const long long* meta, int B, int max_frames, const double* window,
+                     const double* twiddle, const double* crit_filter, double* wss, double* llr, double* snr, void* stream);
+/* out [B][3] = mean of the lowest round(0.95 n) WSS values, the same of the LLR values, plain mean of the segmental SNR */
+int se_metric_trimmed_means(const double* wss, const double* llr, const double* snr, const long long* meta, int B, double* out,
+                            void* stream);
+size_t se_metric_stoi_workspace_bytes(long total_resampled, long total_frames, int B);
+/* STOI: out [B] (NaN where fewer than 30 frames survive the silent-frame removal), d_interm [total_frames] (utterance b: its first
+ * count[b] - 30 entries are the reference's d_interm), count [B] = frames kept; total_* = sums, max_* = maxima of meta columns 5 / 7 */
+int se_metric_stoi(const float* clean, const float* enh, const long long* meta, int B, long total_resampled, long total_frames,
+                   int max_resampled, int max_frames, const double* fir, const double* hann, const double* twiddle,
+                   const double* thirdoct, void* workspace, size_t workspace_bytes, double* d_interm, int* count, double* out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

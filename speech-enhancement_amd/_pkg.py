@@ -14,3 +14,5 @@ from .frontend import disassemble_spectrogram, power_compress, power_uncompress 
 from .diffuse import DiffuSE, inference_schedule  # noqa: F401
 from .diffuse import predict as predict_diffuse  # noqa: F401
 from .tsc_diffusion import TSCNetDiffusion, predict_tsc, tsc_diffusion_step, tsc_diffusion_validation_loss, add_noise  # noqa: F401
+from .train import set_pesq_score_provider  # noqa: F401
+from .metrics import compute_metrics, evaluate  # noqa: F401

@@ -1,7 +1,7 @@
 """inference_gan.py's model loading and per-utterance enhancement (inference_gan.py:60-100) on the HIP path.
 
 Whole-utterance batch-1 forward exactly like the reference (InstanceNorm and attention span the utterance).  The
-metric loop (compute_metrics / librosa / torchaudio) is out of scope."""
+objective-metric loop over the enhanced audio is metrics.evaluate."""
 from collections import OrderedDict
 
 import numpy as np
@@ -93,7 +93,9 @@ class GraphedEnhancer:
         return b
 
     @torch.no_grad()
-    def __call__(self, noisy_signal):
+    def enhance_device(self, noisy_signal):
+        """the enhanced signal as a device tensor [length], complete on the current stream: a view of the bucket's output buffer,
+        valid until the next utterance of the same bucket is enhanced (metrics.evaluate scores it in place)"""
         x = np.asarray(noisy_signal, dtype=np.float32).reshape(-1)
         length, hop = x.shape[0], self.config.HOP_SAMPLES
         frames = int(np.ceil(length / hop))
@@ -104,4 +106,7 @@ class GraphedEnhancer:
         # c = sqrt(L / sum x^2) over the UNPADDED signal: one eager launch writing the scalar the graph reads
         b['c'].copy_(O.clip_scale(b['static_in'][:, :length].contiguous() if pad else b['static_in']))
         b['graph'].replay()
-        return torch.flatten(b['out'])[:length].cpu().numpy()
+        return torch.flatten(b['out'])[:length]
+
+    def __call__(self, noisy_signal):
+        return self.enhance_device(noisy_signal).cpu().numpy()

@@ -1,5 +1,7 @@
-"""inference_gan.py command line (flags :29-52).  Enhances every wav under config.DATA.TEST_NOISY_DIR when a wav
-reader is available (soundfile / scipy.io.wavfile); the objective-metric loop is out of scope."""
+"""inference_gan.py command line (flags :29-52, loop :102-162).  Enhances every wav under config.DATA.TEST_NOISY_DIR, scores it
+against the file of the same name under config.DATA.TEST_CLEAN_DIR on the device (metrics.evaluate) and prints the reference's
+line `pesq csig cbak covl ssnr stoi`; `--validate-epochs` does so for checkpoint_{start..end-1} and names the best epoch.
+Without clean files it only enhances (and saves with --save).  Needs a wav reader (scipy.io.wavfile)."""
 import argparse
 import glob
 import os
@@ -7,6 +9,7 @@ import os
 import numpy as np
 import torch
 
+from . import metrics
 from .config import get_config
 from .inference import load_model, predict
 
@@ -26,20 +29,61 @@ def parse_option(argv=None):
     return args, get_config(args)
 
 
-def main(argv=None):
+def _read(path, config):
     from scipy.io import wavfile
+    sr, x = wavfile.read(path)
+    if sr != config.SAMPLE_RATE:
+        raise RuntimeError(f'{path}: sample rate {sr} != {config.SAMPLE_RATE} (resampling is outside the hot path)')
+    return x.astype(np.float32) / (32768.0 if x.dtype == np.int16 else 1.0)
+
+
+def _save(args, config, path, y):
+    from scipy.io import wavfile
+    wavfile.write(os.path.join(args.output, os.path.basename(path)), config.SAMPLE_RATE, np.asarray(y, dtype=np.float32))
+
+
+def format_metrics(avg):
+    """the reference's line (inference_gan.py:142-147)"""
+    return (f'pesq: {avg[0]:.3f}\t csig: {avg[1]:.3f}\t cbak: {avg[2]:.3f}\t covl: {avg[3]:.3f}\t '
+            f'ssnr: {avg[4]:.3f}\t stoi: {avg[5]:.3f}')
+
+
+def inference(args, config, model_path, data_paths, device):
+    """inference_gan.py:102-127: the six metric sums over the test set for one checkpoint"""
+    model = load_model(model_path, config, device)
+    noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
+    pairs = ((_read(p, config), _read(p.replace(noisy_dir, clean_dir), config)) for p in data_paths)
+    save = (lambda i, est: _save(args, config, data_paths[i], est.cpu().numpy())) if args.save else None
+    return metrics.evaluate(model, config, pairs, on_enhanced=save)
+
+
+def main(argv=None):
     args, config = parse_option(argv)
     device = torch.device('cuda', args.gpu)
-    model = load_model(args.model_path, config, device)
     os.makedirs(args.output, exist_ok=True)
-    for path in sorted(glob.glob(f'{config.DATA.TEST_NOISY_DIR}/*.wav')):
-        sr, x = wavfile.read(path)
-        if sr != config.SAMPLE_RATE:
-            raise RuntimeError(f'{path}: sample rate {sr} != {config.SAMPLE_RATE} (resampling is outside the hot path)')
-        x = x.astype(np.float32) / (32768.0 if x.dtype == np.int16 else 1.0)
-        y = predict(model, config, x, device)
-        if args.save:
-            wavfile.write(os.path.join(args.output, os.path.basename(path)), sr, y.astype(np.float32))
+    noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
+    data_paths = sorted(glob.glob(f'{noisy_dir}/*.wav'))
+    num = len(data_paths)
+    if not all(os.path.exists(p.replace(noisy_dir, clean_dir)) for p in data_paths) or not os.path.isdir(clean_dir):
+        print(f'no clean signals under DATA.TEST_CLEAN_DIR ({clean_dir}): enhancing only, no metrics')
+        model = load_model(args.model_path, config, device)
+        for path in data_paths:
+            y = predict(model, config, _read(path, config), device)
+            if args.save:
+                _save(args, config, path, y)
+        return
+    if args.validate_epochs:
+        best_pesq, best_epoch = 0, 0
+        for epoch in range(args.start, args.end):
+            model_path = os.path.join(args.model_path, 'checkpoint_{:04d}.pth.tar'.format(epoch))
+            avg = inference(args, config, model_path, data_paths, device) / num
+            print('Epoch: {}'.format(epoch))
+            print(format_metrics(avg))
+            if avg[0] > best_pesq:
+                best_pesq, best_epoch = avg[0], epoch
+        print(f'Best epoch: {best_epoch}\t best PESQ: {best_pesq}')
+    else:
+        print(format_metrics(inference(args, config, args.model_path, data_paths, device) / num))
 
 
 if __name__ == '__main__':

@@ -28,6 +28,35 @@ def set_pesq_provider(fn):
     _PESQ_PROVIDER = fn
 
 
+_PESQ_SCORE_PROVIDER = None
+
+
+def set_pesq_score_provider(fn):
+    """fn(clean_list, enhanced_list) -> raw wide-band PESQ scores, one float per pair of 16 kHz numpy signals: the PESQ term of
+    metrics.compute_metrics / metrics.evaluate (the label provider above returns (pesq - 1) / 3.5 tensors and stays as it is)."""
+    global _PESQ_SCORE_PROVIDER
+    _PESQ_SCORE_PROVIDER = fn
+
+
+def have_pesq_scores():
+    """a raw-score provider is set, or the PyPI package `pesq` can be imported"""
+    if _PESQ_SCORE_PROVIDER is not None:
+        return True
+    import importlib.util
+    return importlib.util.find_spec('pesq') is not None
+
+
+def pesq_scores(clean_list, enhanced_list):
+    """utils/compute_metrics.py:61: pesq(16000, clean, enhanced, 'wb') per pair, from the provider or the `pesq` package"""
+    if _PESQ_SCORE_PROVIDER is not None:
+        return [float(v) for v in _PESQ_SCORE_PROVIDER(clean_list, enhanced_list)]
+    try:
+        from pesq import pesq
+    except ImportError as e:
+        raise RuntimeError('no PESQ source: install `pesq` or call train.set_pesq_score_provider(fn)') from e
+    return [float(pesq(16000, c, n, 'wb')) for c, n in zip(clean_list, enhanced_list)]
+
+
 class PesqSideChannel:
     """Runs the PESQ provider off the critical path.  The reference calls batch_pesq between the
     generator and the discriminator step (core/function.py:283-287): a device-to-host copy that waits for the whole
