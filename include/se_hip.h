@@ -573,6 +573,25 @@ int se_metric_stoi(const float* clean, const float* enh, const long long* meta, 
                    const double* thirdoct, void* workspace, size_t workspace_bytes, double* d_interm, int* count, double* out,
                    void* stream);
 
+/* ---- dataset (speech-enhancement_amd/data.py): wav files -> resident 16 kHz corpus -> batches of crops ----
+ * Rational resampler over a ragged batch, zero extension at both ends:
+ *   y[j] = sum_i x[i] h[j down - i up + half],  half = (ntaps - 1) / 2,  j < ceil(n up / down)
+ * (with the taps of metrics.resample_fir this is scipy.signal.resample_poly's default).  x: one arena of int16 PCM (scaled by
+ * 1 / 32768 in the kernel) or fp32, in_total elements; y: one fp32 arena of out_total elements; accumulation in fp32.
+ * utt (device, int64 [n_utt][3]) = (offset in x, length n, offset in y) per utterance; tiles (device, int32 [n_tiles][2]) =
+ * (utterance, first output) per workgroup, each covering `tile` outputs, tile = the value of the _tile query below for this ratio
+ * (0 = unsupported ratio / tap count).  A table row that does not fit in_total / out_total writes nothing. */
+int se_resample_poly_tile(int up, int down, int ntaps);
+int se_resample_poly(const void* x, int x_is_int16, const long long* utt, int n_utt, const int* tiles, int n_tiles, int tile,
+                     const float* taps, int ntaps, int up, int down, float* y, long long in_total, long long out_total,
+                     void* stream);
+/* clean / noisy [B][L] from two arenas of arena_total floats with a common layout; rows (device, int64 [B][3]) = (offset of the
+ * utterance, its length, crop start).  length >= L: out[t] = x[start + t]; length < L: out[t] = x[t mod length] (the reference
+ * collator's tiling, datasets/voicebank_dataset.py:73-83; start is ignored).  stats [B][3] = (sum clean^2, sum noisy^2, max |clean|),
+ * reduced in fp64 in a fixed order.  A row that does not fit the arena is written as zeros. */
+int se_crop_gather(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows, int B, int L,
+                   float* clean, float* noisy, float* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,3 +16,4 @@ from .diffuse import predict as predict_diffuse  # noqa: F401
 from .tsc_diffusion import TSCNetDiffusion, predict_tsc, tsc_diffusion_step, tsc_diffusion_validation_loss, add_noise  # noqa: F401
 from .train import set_pesq_score_provider  # noqa: F401
 from .metrics import compute_metrics, evaluate  # noqa: F401
+from .data import DeviceDataset, DeviceLoader, read_wav, resample  # noqa: F401

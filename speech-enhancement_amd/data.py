@@ -1,0 +1,407 @@
+"""Training data on the device: the VoicebankDataset + Collator of datasets/voicebank_dataset.py without a loader.
+
+    train_set = DeviceDataset(clean_dir, noisy_dir, device='cuda:0')        # decode once, resample on the GPU, keep resident
+    loader = DeviceLoader(train_set, batch_size=16, crop_samples=32000, shuffle=True)
+    for epoch in ...:
+        loader.set_epoch(epoch)
+        for batch in loader:                # {'audio': [b, L], 'noisy': [b, L], 'keys': [(file_index, start), ...]} on the device
+
+Every wav is read once (`read_wav`), resampled to 16 kHz by a HIP kernel (`resample`, csrc/se_data.hip) and kept in two fp32
+arenas; a batch of crops is one launch (`se_crop_gather`) that also returns each row's energy, which is what the loader rejects
+silent crops on.  The resampling filter is scipy.signal.resample_poly's default (Kaiser beta = 5, metrics.resample_fir), NOT
+librosa's soxr_hq: the 16 kHz signals differ slightly from the ones the reference trained on.  There is no CPU fallback."""
+import ctypes as C
+import glob
+import math
+import random
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .metrics import resample_fir
+
+MAX_RATIO = 441                 # 44.1 kHz <-> 16 kHz = 160:441 is the largest tap table the kernel stages (8 821 taps)
+READ_THREADS = 8
+CHUNK_SAMPLES = 1 << 25         # input samples uploaded and resampled at a time (64 MB of PCM16)
+MAX_ATTEMPTS = 10               # the collator's "ten more chances"
+
+
+def _scale_pcm(x):
+    if x.dtype == np.int16:
+        return x.astype(np.float32) / 32768.0
+    if x.dtype == np.int32:
+        return (x.astype(np.float64) / 2147483648.0).astype(np.float32)
+    if x.dtype == np.uint8:
+        return (x.astype(np.float32) - 128.0) / 128.0
+    return x.astype(np.float32)
+
+
+def _read_any(path):
+    """(sample rate, int16 or float32 array [n] or [n, channels]) -- stdlib `wave` for 16-bit PCM, scipy.io.wavfile otherwise"""
+    import wave
+    try:
+        with wave.open(path, 'rb') as w:
+            if w.getsampwidth() == 2 and w.getcomptype() == 'NONE':
+                sr, ch, n = w.getframerate(), w.getnchannels(), w.getnframes()
+                x = np.frombuffer(w.readframes(n), dtype='<i2')
+                return sr, (x.reshape(-1, ch) if ch > 1 else x)
+    except wave.Error:
+        pass                        # not plain PCM (float, extensible, ...): scipy's reader knows more formats
+    try:
+        from scipy.io import wavfile
+    except ImportError as e:
+        raise RuntimeError(f'{path}: not 16-bit PCM, and reading other wav formats needs scipy (scipy.io.wavfile)') from e
+    sr, x = wavfile.read(path)
+    return sr, (x if x.dtype == np.int16 else _scale_pcm(x))
+
+
+def _mono(x):
+    """int16 mono stays int16 (the resampler scales it on the device); anything else becomes float32, channels averaged like
+    librosa.load(mono=True)"""
+    if x.ndim == 1:
+        return x if x.dtype == np.int16 else _scale_pcm(x)
+    return _scale_pcm(x).mean(axis=1, dtype=np.float32)
+
+
+def read_wav(path):
+    """(sample rate, float32 signal in [-1, 1)); multi-channel files become the channel mean"""
+    sr, x = _read_any(path)
+    return sr, _scale_pcm(_mono(x))
+
+
+def _wav_info(path):
+    """(sample rate, frames) from the header where the stdlib can parse it, else from a full read"""
+    import wave
+    try:
+        with wave.open(path, 'rb') as w:
+            return w.getframerate(), w.getnframes()
+    except wave.Error:
+        sr, x = _read_any(path)
+        return sr, x.shape[0]
+
+
+def ratio(sr_in, sr_out):
+    """(up, down) reduced by the gcd"""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in <= 0 or sr_out <= 0:
+        raise ValueError(f'sample rates must be positive (got {sr_in} -> {sr_out})')
+    g = math.gcd(sr_in, sr_out)
+    up, down = sr_out // g, sr_in // g
+    if max(up, down) > MAX_RATIO:
+        raise ValueError(f'resampling {sr_in} -> {sr_out} Hz is the ratio {up}:{down}; the kernel supports up to {MAX_RATIO}')
+    return up, down
+
+
+def out_length(n, up, down):
+    return (n * up + down - 1) // down
+
+
+_TAPS = {}
+
+
+def _taps(up, down, device):
+    key = (up, down, device.type, device.index)
+    if key not in _TAPS:
+        _TAPS[key] = torch.from_numpy(resample_fir(np.float32, up, down)).to(device)
+    return _TAPS[key]
+
+
+def resample_tables(lengths, up, down, tile, in_offsets=None, out_offsets=None):
+    """host tables of se_resample_poly: utt int64 [U][3] = (in offset, length, out offset) and tiles int32 [T][2] = (utterance,
+    first output); offsets default to dense packing in list order"""
+    n = np.asarray(lengths, dtype=np.int64)
+    n_out = (n * up + down - 1) // down
+    ino = np.concatenate([[0], np.cumsum(n)[:-1]]) if in_offsets is None else np.asarray(in_offsets, dtype=np.int64)
+    outo = np.concatenate([[0], np.cumsum(n_out)[:-1]]) if out_offsets is None else np.asarray(out_offsets, dtype=np.int64)
+    utt = np.stack([ino, n, outo], 1).astype(np.int64)
+    per = (n_out + tile - 1) // tile
+    which = np.repeat(np.arange(len(n), dtype=np.int64), per)
+    first = (np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)) * tile
+    return utt, np.stack([which, first], 1).astype(np.int32), n_out
+
+
+def _resample_into(x_arena, lengths, up, down, y_arena, in_offsets=None, out_offsets=None):
+    """launch the resampler for utterances packed in x_arena (int16 or fp32, device) writing into y_arena (fp32, device)"""
+    L.check_cuda(x_arena, y_arena)
+    if x_arena.dtype not in (torch.int16, torch.float32) or y_arena.dtype != torch.float32:
+        raise L.SeHipError(f'the resampler takes int16 or float32 and writes float32 (got {x_arena.dtype} -> {y_arena.dtype})')
+    if not (x_arena.is_contiguous() and y_arena.is_contiguous()):
+        raise L.SeHipError('the resampler takes contiguous arenas')
+    taps = _taps(up, down, x_arena.device)
+    tile = L.lib().se_resample_poly_tile(C.c_int(up), C.c_int(down), C.c_int(taps.numel()))
+    if tile <= 0:
+        raise L.SeHipError(f'se_resample_poly has no tile size for the ratio {up}:{down}')
+    utt, tiles, n_out = resample_tables(lengths, up, down, tile, in_offsets, out_offsets)
+    if len(utt) == 0 or (utt[:, 1] <= 0).any():
+        raise ValueError('resample: empty signal')
+    if (utt[:, 0] < 0).any() or (utt[:, 0] + utt[:, 1]).max() > x_arena.numel() or (utt[:, 2] < 0).any() \
+            or (utt[:, 2] + n_out).max() > y_arena.numel():
+        raise L.SeHipError('resample: an utterance does not fit its arena')
+    dev = x_arena.device
+    utt_d = torch.from_numpy(utt).to(dev, non_blocking=True)
+    tiles_d = torch.from_numpy(tiles).to(dev, non_blocking=True)
+    L.call('se_resample_poly', L.ptr(x_arena), C.c_int(int(x_arena.dtype == torch.int16)), L.ptr(utt_d), C.c_int(len(utt)),
+           L.ptr(tiles_d), C.c_int(len(tiles)), C.c_int(tile), L.ptr(taps), C.c_int(taps.numel()), C.c_int(up), C.c_int(down),
+           L.ptr(y_arena), C.c_longlong(x_arena.numel()), C.c_longlong(y_arena.numel()), L.stream())
+    return n_out
+
+
+def resample(x, sr_in, sr_out):
+    """x: a 1-D device tensor (int16 PCM or float32) or a list of them, resampled from sr_in to sr_out in one launch -> float32
+    tensor(s).  Equal rates return the input."""
+    if int(sr_in) == int(sr_out):
+        return x
+    up, down = ratio(sr_in, sr_out)
+    single = torch.is_tensor(x)
+    xs = [x] if single else list(x)
+    if not xs or not all(torch.is_tensor(t) for t in xs):
+        raise L.SeHipError('resample takes CUDA tensors: there is no CPU fallback')
+    L.check_cuda(*xs)
+    xs = [t.reshape(-1) for t in xs]
+    if len({t.dtype for t in xs}) > 1 or xs[0].dtype not in (torch.int16, torch.float32):
+        xs = [(t.to(torch.float32) / 32768.0 if t.dtype == torch.int16 else t.to(torch.float32)) for t in xs]
+    lengths = [t.numel() for t in xs]
+    arena = xs[0].contiguous() if len(xs) == 1 else torch.cat(xs)
+    n_out = [out_length(n, up, down) for n in lengths]
+    y = torch.empty(sum(n_out), dtype=torch.float32, device=arena.device)
+    _resample_into(arena, lengths, up, down, y)
+    out = list(torch.split(y, n_out))
+    return out[0] if single else out
+
+
+class DeviceDataset:
+    """Every (clean, noisy) pair of a VoiceBank-style directory pair, at `sample_rate`, resident on `device`.
+
+    files[i] = sorted(glob(noisy_dir/*.wav))[i]; its clean twin is the same path with noisy_dir replaced by clean_dir
+    (datasets/voicebank_dataset.py:28,39).  clean / noisy: fp32 arenas; offsets / lengths: where utterance i lives."""
+
+    def __init__(self, clean_dir, noisy_dir, sample_rate=16000, device=None, max_bytes=None):
+        self.clean_dir, self.noisy_dir, self.sample_rate = clean_dir, noisy_dir, int(sample_rate)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise L.SeHipError('DeviceDataset lives on the GPU: there is no CPU fallback')
+        self.files = sorted(glob.glob(f'{noisy_dir}/*.wav'))
+        if not self.files:
+            raise FileNotFoundError(f'no wav files under {noisy_dir}')
+        self.clean_files = [p.replace(noisy_dir, clean_dir) for p in self.files]
+        with ThreadPoolExecutor(max_workers=READ_THREADS) as pool:
+            info_n = list(pool.map(_wav_info, self.files))
+            info_c = list(pool.map(_wav_info, self.clean_files))
+        for p, a, b in zip(self.files, info_n, info_c):
+            if a != b:
+                raise ValueError(f'{p}: the noisy file has {a[1]} samples at {a[0]} Hz, its clean file {b[1]} at {b[0]} Hz')
+            if a[1] <= 0:
+                raise ValueError(f'{p}: empty file')
+        self.rates = [a[0] for a in info_n]
+        self.raw_lengths = [a[1] for a in info_n]
+        self.lengths = [n if sr == self.sample_rate else out_length(n, *ratio(sr, self.sample_rate))
+                        for sr, n in zip(self.rates, self.raw_lengths)]
+        self.offsets = [0] + list(np.cumsum(self.lengths)[:-1].tolist())
+        self.total = int(sum(self.lengths))
+        self.nbytes = 2 * 4 * self.total
+        # + the staging of one chunk of one side (fp32 at worst): at most CHUNK_SAMPLES / 2 samples, or one file if it is longer
+        need = self.nbytes + 4 * min(sum(self.raw_lengths), CHUNK_SAMPLES // 2 + max(self.raw_lengths))
+        if max_bytes is not None and need > max_bytes:
+            raise MemoryError(f'the dataset needs {need} bytes on the device, max_bytes allows {max_bytes}')
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free:
+            raise MemoryError(f'the dataset needs {need} bytes on the device, {free} are free')
+        self.clean = torch.empty(self.total, dtype=torch.float32, device=self.device)
+        self.noisy = torch.empty(self.total, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device), ThreadPoolExecutor(max_workers=READ_THREADS) as pool:
+            i = 0
+            while i < len(self.files):
+                j, acc = i, 0
+                while j < len(self.files) and (j == i or acc + self.raw_lengths[j] <= CHUNK_SAMPLES // 2):
+                    acc += self.raw_lengths[j]
+                    j += 1
+                for paths, arena in ((self.files, self.noisy), (self.clean_files, self.clean)):
+                    self._load(list(range(i, j)), list(pool.map(_read_any, paths[i:j])), paths, arena)
+                i = j
+        torch.cuda.synchronize(self.device)
+
+    def _load(self, idx, read, paths, arena):
+        """one chunk of files into `arena`: files at the target rate are copied, the others grouped by (rate, sample type) and
+        resampled straight into their places"""
+        groups = {}
+        for i, (sr, x) in zip(idx, read):
+            x = _mono(x)
+            if sr != self.rates[i] or x.shape[0] != self.raw_lengths[i]:
+                raise ValueError(f'{paths[i]}: {x.shape[0]} samples at {sr} Hz, its header says {self.raw_lengths[i]} at {self.rates[i]}')
+            if sr == self.sample_rate:
+                x = _scale_pcm(x)
+            groups.setdefault((sr, x.dtype.str), []).append((i, x))
+        for (sr, _), items in groups.items():
+            host = torch.from_numpy(np.ascontiguousarray(np.concatenate([x for _, x in items])))
+            if sr == self.sample_rate:
+                o = 0
+                for i, x in items:
+                    arena[self.offsets[i]:self.offsets[i] + x.shape[0]].copy_(host[o:o + x.shape[0]])
+                    o += x.shape[0]
+                continue
+            up, down = ratio(sr, self.sample_rate)
+            _resample_into(host.to(self.device), [x.shape[0] for _, x in items], up, down, arena,
+                           out_offsets=[self.offsets[i] for i, _ in items])
+
+    def __len__(self):
+        return len(self.files)
+
+    def signal(self, i):
+        """(clean, noisy) views of utterance i"""
+        o, n = self.offsets[i], self.lengths[i]
+        return self.clean[o:o + n], self.noisy[o:o + n]
+
+
+def zero_energy(stats):
+    """the default rejection rule on stats [b, 3] = (sum clean^2, sum noisy^2, max |clean|): a signal without energy, where
+    normalize_batch divides by zero"""
+    return (stats[:, 0] == 0) | (stats[:, 1] == 0)
+
+
+def crop_rng(seed, epoch, rank):
+    """the private stream of crop starts of one (seed, epoch, rank)"""
+    return random.Random(f'se-crop-{int(seed)}-{int(epoch)}-{int(rank)}')
+
+
+def sampler_order(n, world=1, rank=0, shuffle=True, seed=0, epoch=0):
+    """the indices one rank visits in one epoch: torch.utils.data.DistributedSampler(range(n), world, rank, shuffle, seed) after
+    set_epoch(epoch) for world > 1 (padded by wrapping so every rank gets ceil(n / world)); for world == 1 randperm(n) from a
+    generator seeded seed + epoch, or range(n)"""
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(seed + epoch)
+        order = torch.randperm(n, generator=g).tolist()
+    else:
+        order = list(range(n))
+    if world == 1:
+        return order
+    total = -(-n // world) * world
+    pad = total - n
+    order += order[:pad] if pad <= n else (order * -(-pad // n))[:pad]
+    return order[rank:total:world]
+
+
+class _Gathered:
+    """one se_crop_gather launch in flight: the device tensors and the statistics on their way to pinned memory"""
+    __slots__ = ('clean', 'noisy', 'host', 'full', 'event', 'pool')
+
+    def stats(self):
+        """[b, 3] numpy (waits for the copy only); the pinned buffer goes back to the loader"""
+        self.event.synchronize()
+        out = self.host.numpy().copy()
+        self.pool.append(self.full)
+        self.host = self.full = None
+        return out
+
+
+class DeviceLoader:
+    """Batches of random crops of a DeviceDataset: the DataLoader + DistributedSampler + Collator of the reference's main_gan.py.
+
+    Order: `sampler_order`.  Crops: a row with length >= L draws start = randint(0, length - L) from `crop_rng(seed, epoch, rank)`,
+    a shorter row is tiled to L samples and draws nothing.  A row whose statistics `reject` flags (default `zero_energy`; the
+    reference rejects where PESQ throws) is redrawn, all rejected rows of the batch in one pass, up to 10 attempts in all, then
+    dropped -- the batch gets smaller, as in the reference; a tiled row is dropped at once; a batch that loses every row is
+    skipped.  The gather of batch i + 1 is launched before the statistics of batch i are waited for, so the draws of a redraw
+    pass of batch i come after the first draws of batch i + 1 in the stream."""
+
+    def __init__(self, dataset, batch_size, crop_samples, shuffle, seed=0, rank=0, world=1, reject=None):
+        if batch_size < 1 or crop_samples < 1 or not 0 <= rank < world:
+            raise ValueError(f'bad loader geometry: batch {batch_size}, crop {crop_samples}, rank {rank} of {world}')
+        self.dataset, self.batch_size, self.crop_samples, self.shuffle = dataset, int(batch_size), int(crop_samples), bool(shuffle)
+        self.seed, self.rank, self.world, self.epoch = int(seed), int(rank), int(world), 0
+        self.reject = reject if reject is not None else zero_energy
+        self._pinned = []
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def indices(self):
+        return sampler_order(len(self.dataset), self.world, self.rank, self.shuffle, self.seed, self.epoch)
+
+    def __len__(self):
+        return -(-len(self.indices()) // self.batch_size)
+
+    def _draw(self, files, rng):
+        Lc, lengths = self.crop_samples, self.dataset.lengths
+        return [rng.randint(0, lengths[f] - Lc) if lengths[f] >= Lc else -1 for f in files]
+
+    def _gather(self, files, starts):
+        """launch one se_crop_gather for rows (file, start) -> _Gathered"""
+        ds, b, Lc = self.dataset, len(files), self.crop_samples
+        rows = np.empty((b, 3), dtype=np.int64)
+        for r, (f, s) in enumerate(zip(files, starts)):
+            n = ds.lengths[f]
+            if not (0 <= f < len(ds.lengths)) or (n >= Lc and not 0 <= s <= n - Lc):
+                raise L.SeHipError(f'crop ({f}, {s}) is outside utterance {f} of {n} samples')
+            rows[r] = (ds.offsets[f], n, max(s, 0))
+        dev = ds.clean.device
+        g = _Gathered()
+        g.clean = torch.empty(b, Lc, dtype=torch.float32, device=dev)
+        g.noisy = torch.empty(b, Lc, dtype=torch.float32, device=dev)
+        stats = torch.empty(b, 3, dtype=torch.float32, device=dev)
+        rows_d = torch.from_numpy(rows).to(dev, non_blocking=True)
+        with torch.cuda.device(dev):
+            L.call('se_crop_gather', L.ptr(ds.clean), L.ptr(ds.noisy), C.c_longlong(ds.clean.numel()), L.ptr(rows_d), C.c_int(b),
+                   C.c_int(Lc), L.ptr(g.clean), L.ptr(g.noisy), L.ptr(stats), L.stream())
+            full = self._pinned.pop() if self._pinned else torch.empty(self.batch_size, 3, dtype=torch.float32, pin_memory=True)
+            g.full, g.host = full, full[:b]
+            g.host.copy_(stats, non_blocking=True)
+            g.event = torch.cuda.Event()
+            g.event.record()
+        g.pool = self._pinned
+        return g
+
+    def _place(self, g, rows, sub):
+        """rows `rows` of batch g <- the redrawn crops `sub`"""
+        at = torch.as_tensor(rows, device=g.clean.device)
+        g.clean.index_copy_(0, at, sub.clean)
+        g.noisy.index_copy_(0, at, sub.noisy)
+
+    def _select(self, g, keep):
+        at = torch.as_tensor(keep, device=g.clean.device)
+        return g.clean.index_select(0, at), g.noisy.index_select(0, at)
+
+    def _finish(self, files, starts, g, rng):
+        """wait for the statistics of a gathered batch, redraw / drop what they reject -> the item, or None"""
+        starts = list(starts)
+        bad = np.flatnonzero(np.asarray(self.reject(g.stats()), dtype=bool)).tolist()
+        attempt = 1
+        Lc, lengths = self.crop_samples, self.dataset.lengths
+        dropped = [r for r in bad if lengths[files[r]] < Lc]
+        bad = [r for r in bad if lengths[files[r]] >= Lc]
+        while bad and attempt < MAX_ATTEMPTS:
+            sub_files = [files[r] for r in bad]
+            sub_starts = self._draw(sub_files, rng)
+            sub = self._gather(sub_files, sub_starts)
+            self._place(g, bad, sub)
+            for r, s in zip(bad, sub_starts):
+                starts[r] = s
+            still = np.asarray(self.reject(sub.stats()), dtype=bool)
+            bad = [r for r, x in zip(bad, still) if x]
+            attempt += 1
+        dropped = set(dropped + bad)
+        keep = [r for r in range(len(files)) if r not in dropped]
+        if not keep:
+            return None
+        clean, noisy = (g.clean, g.noisy) if not dropped else self._select(g, keep)
+        return {'audio': clean, 'noisy': noisy, 'keys': [(int(files[r]), int(starts[r])) for r in keep]}
+
+    def __iter__(self):
+        rng = crop_rng(self.seed, self.epoch, self.rank)
+        order = self.indices()
+        pending = None
+        for i in range(0, len(order), self.batch_size):
+            files = order[i:i + self.batch_size]
+            starts = self._draw(files, rng)
+            cur = (files, starts, self._gather(files, starts))
+            if pending is not None:
+                item = self._finish(*pending, rng)
+                if item is not None:
+                    yield item
+            pending = cur
+        if pending is not None:
+            item = self._finish(*pending, rng)
+            if item is not None:
+                yield item

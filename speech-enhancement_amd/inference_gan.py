@@ -32,8 +32,10 @@ def parse_option(argv=None):
 def _read(path, config):
     from scipy.io import wavfile
     sr, x = wavfile.read(path)
-    if sr != config.SAMPLE_RATE:
-        raise RuntimeError(f'{path}: sample rate {sr} != {config.SAMPLE_RATE} (resampling is outside the hot path)')
+    if sr != config.SAMPLE_RATE:         # on the current device, with scipy's polyphase default filter (data.py), not librosa's soxr_hq
+        from . import data
+        _, x = data.read_wav(path)
+        return data.resample(torch.from_numpy(x).cuda(), sr, config.SAMPLE_RATE).cpu().numpy()
     return x.astype(np.float32) / (32768.0 if x.dtype == np.int16 else 1.0)
 
 

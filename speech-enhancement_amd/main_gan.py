@@ -4,9 +4,10 @@
         --crop-len 2 --synthetic 8
 
 One process per GPU: launch N processes with torch.distributed.run (env:// rendezvous); `--multiprocessing-distributed`
-spawns them itself like the reference.  The VoiceBank dataset / collator (librosa + pesq) is out of scope; with
-`--synthetic N` the loaders are N synthetic batches per epoch with PESQ labels supplied (the bench's data recipe),
-otherwise `speech_enhancement_amd.main_gan.DATASET_FACTORY` must be set to a callable returning (train, valid) loaders.
+spawns them itself like the reference.  With `--synthetic N` the loaders are N synthetic batches per epoch with PESQ labels
+supplied (the bench's data recipe); else `speech_enhancement_amd.main_gan.DATASET_FACTORY`, when set, is a callable returning
+(train, valid) loaders; else the four `config.DATA.*_DIR` wav folders become device-resident datasets (data.py: decoded once,
+resampled to 16 kHz on the GPU, one launch per batch of crops) and the PESQ labels come from the provider (train.py).
 """
 import argparse
 import os
@@ -79,6 +80,20 @@ def synthetic_loader(n_batches, batch, samples, seed):
     return out
 
 
+def device_loaders(args, config, samples):
+    """main_gan.py:222-253 on the device (data.py): both corpora resident on this rank's GPU, the per-rank batch size, and the
+    reference's sampling -- shuffled when there is no sampler (train) or a DistributedSampler with its defaults (both)"""
+    from . import data
+    dev = torch.device('cuda', args.gpu)
+    rank, world = (args.rank, args.world_size) if args.distributed else (0, 1)
+    train_set = data.DeviceDataset(config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR, config.SAMPLE_RATE, device=dev)
+    valid_set = data.DeviceDataset(config.DATA.TEST_CLEAN_DIR, config.DATA.TEST_NOISY_DIR, config.SAMPLE_RATE, device=dev)
+    print('Audio signals cropped to {} seconds long'.format(config.CROP_LEN))
+    train_loader = data.DeviceLoader(train_set, args.batch_size, samples, shuffle=True, rank=rank, world=world)
+    valid_loader = data.DeviceLoader(valid_set, args.batch_size, samples, shuffle=args.distributed, rank=rank, world=world)
+    return train_loader, valid_loader
+
+
 def main_worker(gpu, ngpus_per_node, args, config):
     args.gpu = gpu
     if args.distributed:
@@ -125,6 +140,9 @@ def main_worker(gpu, ngpus_per_node, args, config):
         valid_loader = train_loader[:1]
     elif DATASET_FACTORY is not None:
         train_loader, valid_loader = DATASET_FACTORY(args, config)
+    elif all(os.path.isdir(d) for d in (config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR, config.DATA.TEST_CLEAN_DIR,
+                                        config.DATA.TEST_NOISY_DIR)):
+        train_loader, valid_loader = device_loaders(args, config, samples)
     else:
         raise RuntimeError('the VoiceBank dataset / collator is outside this package: pass --synthetic N or set '
                            'speech_enhancement_amd.main_gan.DATASET_FACTORY')
@@ -133,6 +151,9 @@ def main_worker(gpu, ngpus_per_node, args, config):
     if not args.distributed or args.rank == 0:
         logging.basicConfig(level=logging.INFO)
     for epoch in range(args.start_epoch, args.epochs):
+        for loader in (train_loader, valid_loader):
+            if hasattr(loader, 'set_epoch'):
+                loader.set_epoch(epoch)
         tg, td = train_gan(train_loader, model, discriminator, criterion, optimizer, optimizer_disc, logger, epoch, args,
                            config)
         vg, vd = validate_gan(valid_loader, model, discriminator, criterion, logger, epoch, args, config)
