@@ -592,6 +592,31 @@ int se_resample_poly(const void* x, int x_is_int16, const long long* utt, int n_
 int se_crop_gather(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows, int B, int L,
                    float* clean, float* noisy, float* stats, void* stream);
 
+/* ---- reverse-diffusion sampler of the TSC hybrid (speech-enhancement_amd/sampler.py; inference_diffuse.py:231-269) ----
+ * The step index n (device int32), the utterance counter run (device uint32) and the seed (device uint64) are read on the device,
+ * so one captured reverse step serves every step of every utterance.
+ * Gaussian noise: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), key = (seed low,
+ * seed high), counter = (group low, group high, n, run), group = flat element index / 4: one call gives the draws of elements
+ * 4g .. 4g + 3.  u = (w + 0.5) 2^-32; words 0, 1 -> z = sqrt(-2 ln u0) (cos, sin)(2 pi u1), words 2, 3 the second pair (accurate
+ * logf / cosf / sinf).  A draw depends on (seed, run, n, element) only.
+ *
+ * se_sampler_update: audio [B][L] in place (any L > 0, rows need not be 16-byte aligned), coef [steps][4] = (c1, c2, c3, sigma):
+ *   n > 0:  audio = c1 audio + c2 noisy - c3 eps + sigma z,  z = noise [steps - 1][B][L] at index steps - 1 - n, or drawn (noise NULL)
+ *   n == 0: audio = (1 - gamma) (c1 audio - c3 eps) + gamma noisy, then clamped to [-1, 1] if clamp != 0, then multiplied by
+ *           1 / c_inv[b] if c_inv (the clip scales c [B]) is given
+ * The launch only reads n; a step outside [0, steps) writes nothing. */
+int se_sampler_update(float* audio, const float* noisy, const float* eps, const float* coef, const int* n, int steps,
+                      const float* noise, const unsigned long long* seed, const unsigned* run, const float* c_inv, float gamma,
+                      int clamp, int B, long long L, void* stream);
+/* after the update in stream order: n <- n - 1; where n was 0: n <- steps - 1 and run <- run + 1; d [64] <- row n of emb [steps][64] */
+int se_sampler_advance(int* n, unsigned* run, int steps, const float* emb, float* d, void* stream);
+/* audio = noisy = wrap_pad(x) c: x [B][length], c [B], outputs [B][padded]; element i >= length repeats element i - length */
+int se_sampler_begin(const float* x, const float* c, float* audio, float* noisy, int B, int length, int padded, void* stream);
+/* the generator alone: groups first_group .. first_group + n_groups - 1 (mod 2^64) with counter words 2, 3 = (c2, c3);
+ * out_words [n_groups][4] raw 32-bit words and / or out_normals [n_groups][4] (either may be NULL) */
+int se_philox_normal(unsigned long long seed, unsigned c2, unsigned c3, unsigned long long first_group, long long n_groups,
+                     unsigned* out_words, float* out_normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,15 @@ def lib():
         for f in ('se_attn_bwd_workspace_bytes', 'se_norm_prelu_bwd_workspace_bytes', 'se_segnorm_workspace_bytes',
                   'se_dwconv31_wgrad_workspace_bytes', 'se_disc_tail_workspace_bytes', 'se_metric_stoi_workspace_bytes'):
             getattr(_lib, f).restype = C.c_size_t
+        # the sampler entries take 64-bit integers by value (seed, group index, row length): declared, not left to ctypes' int default
+        # (an SE_HIP_LIB build from before the sampler has none of them: it still loads, and calling one raises)
+        p, i, u, q, f32 = C.c_void_p, C.c_int, C.c_uint, C.c_longlong, C.c_float
+        for name, argtypes in (('se_sampler_update', [p, p, p, p, p, i, p, p, p, p, f32, i, i, q, p]),
+                               ('se_sampler_advance', [p, p, i, p, p, p]),
+                               ('se_sampler_begin', [p, p, p, p, i, i, i, p]),
+                               ('se_philox_normal', [C.c_ulonglong, u, u, C.c_ulonglong, q, p, p, p])):
+            if hasattr(_lib, name):
+                getattr(_lib, name).argtypes = argtypes
     return _lib
 
 

@@ -46,13 +46,15 @@ class TSCNetDiffusion(TSCNet):
         self.merge_block = mb
         self._pnames = [k for k, _ in self.named_parameters()]
 
-    def _merge(self, P, x, cond, step, B):
+    def _merge(self, P, x, cond, step, B, d=None):
         """MergeBlock.forward (tsc_diffusion.py:27-40) on tokens [M, 64]: y = W_m (x + d) + b_m + W_c cond + b_c;
         out = (x + W_r (sigmoid(gate) tanh(filter)) + b_r) / sqrt(2).  d = the projected step embedding: with ONE step for the
-        whole batch (predict_tsc) it folds into the bias (W_m d + b_m, weight-sized); per-clip steps add d to x first."""
+        whole batch (predict_tsc) it folds into the bias (W_m d + b_m, weight-sized); per-clip steps add d to x first.  A caller
+        that holds the projected embedding already (the graphed sampler: a [1, 64] device buffer) passes it as `d`."""
         M = x.shape[0]
         mb = self.merge_block
-        d = mb.diffusion_projection(mb.diffusion_embedding(step))                      # [N, 64], host-sized plumbing
+        if d is None:
+            d = mb.diffusion_projection(mb.diffusion_embedding(step))                  # [N, 64], host-sized plumbing
         Wm, Wc = P['merge_block.merge_diffusion.weight'].view(128, 64), P['merge_block.conditioner_projection.weight'].view(128, 64)
         Wr = P['merge_block.output_residual.weight'].view(64, 64)
         if d.shape[0] == 1:
@@ -74,21 +76,24 @@ class TSCNetDiffusion(TSCNet):
         return O.axpbypcz(x, res, res, r2, r2, 0.0)
 
     @torch.no_grad()
-    def forward_planes(self, xin, nin, diffusion_step):
-        """xin / nin: planes [B, T, F, 4] of the current and of the conditioning spectrum -> est planes [B, T, F, 4]"""
+    def forward_planes(self, xin, nin, diffusion_step, d=None):
+        """xin / nin: planes [B, T, F, 4] of the current and of the conditioning spectrum -> est planes [B, T, F, 4].
+        d (optional): the projected step embedding [1, 64] on the device, used instead of the embedding MLP of diffusion_step"""
         if self.training:
             raise L.SeHipError('TSCNetDiffusion is an inference path (eval mode): call .eval() first')
         P = dict(self.named_parameters())
         P.update(dict(self.named_buffers()))
         P['__prep__'] = self._prepare_weights(P, xin.device)
         B, T, Fq, _ = xin.shape
-        step = torch.as_tensor(diffusion_step, device=xin.device)
+        if d is not None and (tuple(d.shape) != (1, 64) or d.device != xin.device or d.dtype != torch.float32):
+            raise L.SeHipError('TSCNetDiffusion: d must be a float32 [1, 64] tensor on the device of the planes')
+        step = None if d is not None else torch.as_tensor(diffusion_step, device=xin.device)
         x, _ = LY.encoder_fwd(P, xin.contiguous(), B, T, Fq)
         xn, _ = LY.encoder_fwd(P, nin.contiguous(), B, T, Fq, p='dense_encoder_noisy')
         Fp = x.shape[2]
         tok, cond = x.view(B * T * Fp, 64), xn.view(B * T * Fp, 64)
         for i in range(1, 5):
-            tok = self._merge(P, tok, cond, step, B)
+            tok = self._merge(P, tok, cond, step, B, d)
             tok, _ = LY.conformer_fwd(P, f'TSCB_{i}.time_conformer', tok, B, T, Fp, 'time', False)
             tok, _ = LY.conformer_fwd(P, f'TSCB_{i}.freq_conformer', tok, B, T, Fp, 'freq', False)
         cplx, _ = LY.complex_decoder_fwd(P, tok, B, T, Fp)
