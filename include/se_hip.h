@@ -591,6 +591,28 @@ int se_resample_poly(const void* x, int x_is_int16, const long long* utt, int n_
  * reduced in fp64 in a fixed order.  A row that does not fit the arena is written as zeros. */
 int se_crop_gather(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows, int B, int L,
                    float* clean, float* noisy, float* stats, void* stream);
+/* The crop gather with the noise of another utterance mixed in at a drawn SNR ("remix"): the noise of every file is addressable as
+ * noisy_arena - clean_arena because the arenas share their layout.  rows (device, int64 [B][6]) = (off_s, len_s, start_s, off_n,
+ * len_n, start_n): the speech source and the noise source, each with the index rule of se_crop_gather: i(t) = start + t when
+ * len >= L, otherwise t mod len with start ignored.  gain (device, [B]) = 10^(-snr_dB / 20), computed by the host in fp64.
+ *   c[t] = clean_arena[off_s + i_s(t)]
+ *   d[t] = noisy_arena[off_n + i_n(t)] - clean_arena[off_n + i_n(t)]                    (one fp32 subtraction)
+ *   Pc = sum c^2, Pd = sum d^2 in fp64 in a fixed order: within a chunk of SE_MIX_CHUNK samples thread t of 256 takes samples
+ *        t, t + 256, ..., then wave shuffles, then the four waves in index order (as se_crop_gather); the chunks in index order
+ *   a = (float)(sqrt(Pc / Pd) * gain[b])
+ *   clean[b][t] = c[t],  noisy[b][t] = fmaf(a, d[t], c[t]),  scale[b] = a
+ * off_n < 0 = the row is not mixed: noisy[b][t] = noisy_arena[off_s + i_s(t)], bit for bit what se_crop_gather writes, and
+ * scale[b] = 0.  A row falls back to exactly that form, with scale[b] = 0, when its noise source does not fit the arena, when
+ * Pd == 0 or Pc == 0, or when a is not finite or is zero.  A speech source that does not fit the arena writes zeros (scale 0).
+ * stats [B][nchunk][3], nchunk = ceil(L / SE_MIX_CHUNK): per-chunk partials (sum clean^2, sum noisy_out^2, max |clean|) of what was
+ * written, for the caller to add in index order.  workspace: B * nchunk * 2 doubles, 8-byte aligned (the query returns 0 for
+ * non-positive sizes).  Two launches with a grid of (chunk, row): the first leaves the per-chunk (Pc, Pd) in the workspace, in the
+ * second every workgroup of a row adds them in index order, so all of them apply the same a.  B <= 65535, L <= 2^30. */
+#define SE_MIX_CHUNK 4096
+size_t se_crop_gather_mix_workspace_bytes(int B, int L);
+int se_crop_gather_mix(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows,
+                       const double* gain, int B, int L, float* clean, float* noisy, double* stats, float* scale, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- reverse-diffusion sampler of the TSC hybrid (speech-enhancement_amd/sampler.py; inference_diffuse.py:231-269) ----
  * The step index n (device int32), the utterance counter run (device uint32) and the seed (device uint64) are read on the device,

@@ -61,9 +61,13 @@ def lib():
         for name, argtypes in (('se_sampler_update', [p, p, p, p, p, i, p, p, p, p, f32, i, i, q, p]),
                                ('se_sampler_advance', [p, p, i, p, p, p]),
                                ('se_sampler_begin', [p, p, p, p, i, i, i, p]),
-                               ('se_philox_normal', [C.c_ulonglong, u, u, C.c_ulonglong, q, p, p, p])):
+                               ('se_philox_normal', [C.c_ulonglong, u, u, C.c_ulonglong, q, p, p, p]),
+                               ('se_crop_gather_mix', [p, p, q, p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
+                               ('se_crop_gather_mix_workspace_bytes', [i, i])):
             if hasattr(_lib, name):
                 getattr(_lib, name).argtypes = argtypes
+        if hasattr(_lib, 'se_crop_gather_mix_workspace_bytes'):
+            _lib.se_crop_gather_mix_workspace_bytes.restype = C.c_size_t
     return _lib
 
 

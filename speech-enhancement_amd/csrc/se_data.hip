@@ -160,3 +160,185 @@ extern "C" int se_crop_gather(const float* clean_arena, const float* noisy_arena
                      clean, noisy, stats);
   return se_check_launch("se_crop_gather");
 }
+
+// The crop gather with the noise of another utterance mixed in at a drawn SNR (definition: include/se_hip.h).  A row is spread over
+// nchunk = ceil(L / SE_MIX_CHUNK) workgroups, grid (chunk, row), in two launches: the first leaves every chunk's (sum c^2, sum d^2) in
+// the workspace, the second has every workgroup of a row add that row's partials in index order -- all of them get the same a --
+// and write its chunk.  No atomics, no counters: the launch boundary is the only hand-off.
+constexpr int MIX_CHUNK = 4096;
+
+struct MixRow {
+  const float* cs;        // clean arena at the speech crop (index i_s(t))
+  const float* vs;        // noisy arena at the speech crop
+  const float* cn;        // clean arena at the noise crop (index i_n(t))
+  const float* vn;        // noisy arena at the noise crop
+  int len_s, len_n;       // tiling periods, 0 = not tiled
+  bool ok, mix;           // the speech source fits the arena; so does the noise source, and the row asks for it
+};
+
+// where a source (offset, length, start) of L samples lies in an arena of `total`: false if it does not fit
+static __device__ __forceinline__ bool mix_source(long long off, long long len, long long start, int L, long long total,
+                                                  long long* first, int* period) {
+  const bool tiled = len < L;
+  if (tiled) start = 0;
+  *first = off + start;
+  *period = tiled ? (int)len : 0;
+  return off >= 0 && len >= 1 && off <= total && len <= total - off && start >= 0 && (tiled || start <= len - L);
+}
+
+static __device__ __forceinline__ MixRow mix_row(const float* __restrict__ clean_arena, const float* __restrict__ noisy_arena,
+                                                 const long long* __restrict__ rows, int b, int L, long long arena_total) {
+  const long long* r = rows + 6 * (size_t)b;
+  MixRow m;
+  long long fs = 0, fn = 0;
+  m.ok = mix_source(r[0], r[1], r[2], L, arena_total, &fs, &m.len_s);
+  m.mix = m.ok && r[3] >= 0 && mix_source(r[3], r[4], r[5], L, arena_total, &fn, &m.len_n);
+  if (!m.ok) fs = 0;
+  if (!m.mix) fn = 0;                                   // never dereferenced then; keeps the pointers inside the arena anyway
+  m.cs = clean_arena + fs;
+  m.vs = noisy_arena + fs;
+  m.cn = clean_arena + fn;
+  m.vn = noisy_arena + fn;
+  return m;
+}
+
+// block sum of (x, y) in the order of crop_gather_kernel: wave shuffles, then the four waves in index order; valid in thread 0
+static __device__ __forceinline__ void mix_block_sum(double& x, double& y, double (*red)[CG_THREADS / 64]) {
+  x = wave_sum_d(x);
+  y = wave_sum_d(y);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[0][w] = x;
+    red[1][w] = y;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    x = y = 0.0;
+    for (int k = 0; k < CG_THREADS / 64; ++k) {
+      x += red[0][k];
+      y += red[1][k];
+    }
+  }
+}
+
+__global__ __launch_bounds__(CG_THREADS) void crop_mix_power_kernel(const float* __restrict__ clean_arena,
+                                                                    const float* __restrict__ noisy_arena,
+                                                                    const long long* __restrict__ rows, int L, long long arena_total,
+                                                                    double* __restrict__ part) {
+  __shared__ double red[2][CG_THREADS / 64];
+  const int b = blockIdx.y, k = blockIdx.x, nchunk = gridDim.x;
+  const MixRow m = mix_row(clean_arena, noisy_arena, rows, b, L, arena_total);
+  const int t1 = (int)min((long long)L, (long long)(k + 1) * MIX_CHUNK);
+  double pc = 0.0, pd = 0.0;
+  if (m.mix) {
+#pragma unroll 4
+    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) {
+      const int is = m.len_s ? t % m.len_s : t, in = m.len_n ? t % m.len_n : t;
+      const float c = m.cs[is];
+      const float d = m.vn[in] - m.cn[in];
+      pc += (double)c * c;
+      pd += (double)d * d;
+    }
+  }
+  mix_block_sum(pc, pd, red);
+  if (threadIdx.x == 0) {
+    double* p = part + 2 * ((size_t)b * nchunk + k);
+    p[0] = pc;
+    p[1] = pd;
+  }
+}
+
+__global__ __launch_bounds__(CG_THREADS) void crop_mix_write_kernel(const float* __restrict__ clean_arena,
+                                                                    const float* __restrict__ noisy_arena,
+                                                                    const long long* __restrict__ rows,
+                                                                    const double* __restrict__ gain, int L, long long arena_total,
+                                                                    const double* __restrict__ part, float* __restrict__ clean,
+                                                                    float* __restrict__ noisy, double* __restrict__ stats,
+                                                                    float* __restrict__ scale) {
+  __shared__ double red[2][CG_THREADS / 64];
+  __shared__ float redm[CG_THREADS / 64];
+  const int b = blockIdx.y, k = blockIdx.x, nchunk = gridDim.x;
+  const MixRow m = mix_row(clean_arena, noisy_arena, rows, b, L, arena_total);
+  // every workgroup of the row adds the same partials in the same order: one a per row without a word passed between them
+  float a = 0.f;
+  if (m.mix) {
+    double pc = 0.0, pd = 0.0;
+    const double* p = part + 2 * (size_t)b * nchunk;
+    for (int j = 0; j < nchunk; ++j) {
+      pc += p[2 * j];
+      pd += p[2 * j + 1];
+    }
+    if (pc > 0.0 && pd > 0.0) a = (float)(sqrt(pc / pd) * gain[b]);
+    if (!isfinite(a)) a = 0.f;
+  }
+  const bool mix = a != 0.f;
+  const int t1 = (int)min((long long)L, (long long)(k + 1) * MIX_CHUNK);
+  float* co = clean + (size_t)b * L;
+  float* no = noisy + (size_t)b * L;
+  double sc = 0.0, sn = 0.0;
+  float mx = 0.f;
+  if (!m.ok) {                                          // a speech source outside the arena: silence, which the loader rejects
+    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) co[t] = no[t] = 0.f;
+  } else if (mix) {
+#pragma unroll 4
+    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) {
+      const int is = m.len_s ? t % m.len_s : t, in = m.len_n ? t % m.len_n : t;
+      const float c = m.cs[is];
+      const float d = m.vn[in] - m.cn[in];
+      const float v = fmaf(a, d, c);
+      co[t] = c;
+      no[t] = v;
+      sc += (double)c * c;
+      sn += (double)v * v;
+      mx = fmaxf(mx, fabsf(c));
+    }
+  } else {                                              // unmixed, or fallen back: what crop_gather_kernel writes
+#pragma unroll 4
+    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) {
+      const int is = m.len_s ? t % m.len_s : t;
+      const float c = m.cs[is], v = m.vs[is];
+      co[t] = c;
+      no[t] = v;
+      sc += (double)c * c;
+      sn += (double)v * v;
+      mx = fmaxf(mx, fabsf(c));
+    }
+  }
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = mx;
+  mix_block_sum(sc, sn, red);                           // its barrier also covers redm
+  if (threadIdx.x == 0) {
+    for (int j = 0; j < CG_THREADS / 64; ++j) mx = fmaxf(mx, redm[j]);
+    double* s = stats + 3 * ((size_t)b * nchunk + k);
+    s[0] = sc;
+    s[1] = sn;
+    s[2] = (double)mx;
+    if (k == 0) scale[b] = mix ? a : 0.f;
+  }
+}
+
+extern "C" size_t se_crop_gather_mix_workspace_bytes(int B, int L) {
+  if (B <= 0 || L <= 0) return 0;
+  return (size_t)B * (size_t)cdiv(L, MIX_CHUNK) * 2 * sizeof(double);
+}
+
+extern "C" int se_crop_gather_mix(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows,
+                                  const double* gain, int B, int L, float* clean, float* noisy, double* stats, float* scale,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  static_assert(MIX_CHUNK == SE_MIX_CHUNK && MIX_CHUNK % CG_THREADS == 0, "the chunk of the header is the chunk of the kernels");
+  SE_REQUIRE(clean_arena && noisy_arena && rows && gain && clean && noisy && stats && scale && workspace,
+             "crop_gather_mix: null operand");
+  // L: the sample counter of a thread runs up to L + 255 in an int
+  SE_REQUIRE(B > 0 && B <= 65535 && L > 0 && L <= (1 << 30) && arena_total > 0,
+             "crop_gather_mix: bad sizes (B %d, L %d, arena %lld)", B, L, arena_total);
+  SE_REQUIRE(workspace_bytes >= se_crop_gather_mix_workspace_bytes(B, L) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+             "crop_gather_mix: the workspace has %zu bytes, %zu are needed (8-byte aligned)", workspace_bytes,
+             se_crop_gather_mix_workspace_bytes(B, L));
+  const dim3 grid(cdiv(L, MIX_CHUNK), B);
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(crop_mix_power_kernel, grid, dim3(CG_THREADS), 0, as_stream(stream), clean_arena, noisy_arena, rows, L,
+                     arena_total, part);
+  hipLaunchKernelGGL(crop_mix_write_kernel, grid, dim3(CG_THREADS), 0, as_stream(stream), clean_arena, noisy_arena, rows, gain, L,
+                     arena_total, part, clean, noisy, stats, scale);
+  return se_check_launch("se_crop_gather_mix");
+}

@@ -8,7 +8,8 @@
 
 Every wav is read once (`read_wav`), resampled to 16 kHz by a HIP kernel (`resample`, csrc/se_data.hip) and kept in two fp32
 arenas; a batch of crops is one launch (`se_crop_gather`) that also returns each row's energy, which is what the loader rejects
-silent crops on.  The resampling filter is scipy.signal.resample_poly's default (Kaiser beta = 5, metrics.resample_fir), NOT
+silent crops on.  `DeviceLoader(..., remix=Remix(prob, (lo, hi)))` pairs a row's speech crop with the noise (noisy - clean) of another
+utterance at a drawn SNR, in the same two-launch gather (`se_crop_gather_mix`).  The resampling filter is scipy.signal.resample_poly's default (Kaiser beta = 5, metrics.resample_fir), NOT
 librosa's soxr_hq: the 16 kHz signals differ slightly from the ones the reference trained on.  There is no CPU fallback."""
 import ctypes as C
 import glob
@@ -26,6 +27,7 @@ MAX_RATIO = 441                 # 44.1 kHz <-> 16 kHz = 160:441 is the largest t
 READ_THREADS = 8
 CHUNK_SAMPLES = 1 << 25         # input samples uploaded and resampled at a time (64 MB of PCM16)
 MAX_ATTEMPTS = 10               # the collator's "ten more chances"
+MIX_CHUNK = 4096                # SE_MIX_CHUNK of include/se_hip.h
 
 
 def _scale_pcm(x):
@@ -265,6 +267,95 @@ def crop_rng(seed, epoch, rank):
     return random.Random(f'se-crop-{int(seed)}-{int(epoch)}-{int(rank)}')
 
 
+def mix_rng(seed, epoch, rank):
+    """the private stream of noise draws of one (seed, epoch, rank): its own, so the crop starts of a loader do not move when
+    remixing is switched on"""
+    return random.Random(f'se-mix-{int(seed)}-{int(epoch)}-{int(rank)}')
+
+
+class Remix:
+    """Dynamic mixing: with probability `prob` a row's noise is replaced by the noise of a uniformly drawn utterance (its own
+    included), scaled so that the crop's SNR is uniform in snr_db = (lo, hi) dB.  Gain augmentation is not part of it:
+    normalize_batch rescales every pair by the noisy energy."""
+
+    def __init__(self, prob, snr_db=(0.0, 20.0)):
+        prob = float(prob)
+        lo, hi = (float(v) for v in snr_db)
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError(f'remix probability {prob} is outside [0, 1]')
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+            raise ValueError(f'remix SNR bounds ({lo}, {hi}) are not finite')
+        if lo > hi:
+            raise ValueError(f'remix SNR bounds ({lo}, {hi}): the lower one is the larger')
+        self.prob, self.snr_db = prob, (lo, hi)
+
+    def __repr__(self):
+        return f'Remix({self.prob}, snr_db={self.snr_db})'
+
+
+def draw_mix(files, lengths, crop_samples, rng, remix):
+    """the noise of every row of `files`, in order: (noise file, noise start, snr dB) or None for a row that keeps its own noise.
+    Every row consumes the same draws whether it is mixed or not -- u = random(), j = randrange(N), the start
+    randint(0, len_j - L) (none when len_j < L: the noise is tiled, start -1), snr = uniform(lo, hi) -- and is mixed iff u < prob."""
+    out = []
+    lo, hi = remix.snr_db
+    for _ in files:
+        u = rng.random()
+        j = rng.randrange(len(lengths))
+        start = rng.randint(0, lengths[j] - crop_samples) if lengths[j] >= crop_samples else -1
+        snr = rng.uniform(lo, hi)
+        out.append((j, start, snr) if u < remix.prob else None)
+    return out
+
+
+def mix_chunks(samples):
+    """workgroups (chunks of SE_MIX_CHUNK samples) a row of se_crop_gather_mix is spread over"""
+    return -(-int(samples) // MIX_CHUNK)
+
+
+def _launch_mix(dataset, rows, snr_db, samples):
+    """one se_crop_gather_mix for rows int64 [b, 6] (include/se_hip.h) and the SNR of every row -> clean [b, L], noisy [b, L] and the
+    launch's doubles: tail = buf[2 b nchunk:] holds the statistics [b][nchunk][3] followed by the scales (b floats)"""
+    b, n = len(rows), mix_chunks(samples)
+    dev = dataset.clean.device
+    host = np.empty(7 * b, dtype=np.int64)              # the row table and the gains in one upload
+    host[:6 * b] = np.asarray(rows, dtype=np.int64).reshape(-1)
+    host[6 * b:].view(np.float64)[:] = [10.0 ** (-float(v) / 20.0) for v in snr_db]
+    clean = torch.empty(b, samples, dtype=torch.float32, device=dev)
+    noisy = torch.empty(b, samples, dtype=torch.float32, device=dev)
+    buf = torch.empty(5 * b * n + (b + 1) // 2, dtype=torch.float64, device=dev)
+    table = torch.from_numpy(host).to(dev, non_blocking=True)
+    need = L.lib().se_crop_gather_mix_workspace_bytes(b, samples)
+    if need != 16 * b * n:
+        raise L.SeHipError(f'se_crop_gather_mix wants {need} workspace bytes for B {b}, L {samples}: {16 * b * n} were laid out')
+    at, base = table.data_ptr(), buf.data_ptr()           # addresses inside the two buffers: a tensor view each costs microseconds
+    with torch.cuda.device(dev):
+        L.call('se_crop_gather_mix', L.ptr(dataset.clean), L.ptr(dataset.noisy), dataset.clean.numel(), C.c_void_p(at),
+               C.c_void_p(at + 48 * b), b, samples, L.ptr(clean), L.ptr(noisy), C.c_void_p(base + 16 * b * n),
+               C.c_void_p(base + 40 * b * n), C.c_void_p(base), need, L.stream())
+    return clean, noisy, buf[2 * b * n:]
+
+
+def _sum_chunks(tail, b, n):
+    """host copy of a launch's tail -> (stats [b, 3] float64: the chunk partials added in index order, scale [b] float32)"""
+    part = tail[:3 * b * n].reshape(b, n, 3)
+    stats = np.empty((b, 3), dtype=np.float64)
+    stats[:, :2] = np.cumsum(part[:, :, :2], axis=1)[:, -1]        # a running sum: chunk 0, + chunk 1, ... (np.sum may add pairwise)
+    stats[:, 2] = part[:, :, 2].max(axis=1)
+    return stats, tail[3 * b * n:].view(np.float32)[:b].copy()
+
+
+def mix_at_snr(dataset, i, j, snr_db, noise_start=0):
+    """(clean, noisy) device tensors of the whole utterance i with the noise of utterance j at snr_db: noise samples
+    noise_start ... when j is at least as long as i, else j's noise tiled.  Silent noise or speech returns the pair as stored."""
+    n, m = dataset.lengths[i], dataset.lengths[j]
+    if m >= n and not 0 <= noise_start <= m - n:
+        raise ValueError(f'noise start {noise_start} leaves utterance {j} of {m} samples ({n} are needed)')
+    rows = [[dataset.offsets[i], n, 0, dataset.offsets[j], m, noise_start if m >= n else 0]]
+    clean, noisy, _ = _launch_mix(dataset, rows, [snr_db], n)
+    return clean[0], noisy[0]
+
+
 def sampler_order(n, world=1, rank=0, shuffle=True, seed=0, epoch=0):
     """the indices one rank visits in one epoch: torch.utils.data.DistributedSampler(range(n), world, rank, shuffle, seed) after
     set_epoch(epoch) for world > 1 (padded by wrapping so every rank gets ceil(n / world)); for world == 1 randperm(n) from a
@@ -296,6 +387,18 @@ class _Gathered:
         return out
 
 
+class _GatheredMix(_Gathered):
+    """one se_crop_gather_mix in flight; `scale` [b] (0 = the row kept its own noise) is there once stats() has returned"""
+    __slots__ = ('chunks', 'scale')
+
+    def stats(self):
+        self.event.synchronize()
+        out, self.scale = _sum_chunks(self.host.numpy(), self.clean.shape[0], self.chunks)
+        self.pool.append(self.full)
+        self.host = self.full = None
+        return out
+
+
 class DeviceLoader:
     """Batches of random crops of a DeviceDataset: the DataLoader + DistributedSampler + Collator of the reference's main_gan.py.
 
@@ -304,15 +407,23 @@ class DeviceLoader:
     reference rejects where PESQ throws) is redrawn, all rejected rows of the batch in one pass, up to 10 attempts in all, then
     dropped -- the batch gets smaller, as in the reference; a tiled row is dropped at once; a batch that loses every row is
     skipped.  The gather of batch i + 1 is launched before the statistics of batch i are waited for, so the draws of a redraw
-    pass of batch i come after the first draws of batch i + 1 in the stream."""
+    pass of batch i come after the first draws of batch i + 1 in the stream.
 
-    def __init__(self, dataset, batch_size, crop_samples, shuffle, seed=0, rank=0, world=1, reject=None):
+    remix: a `Remix`, or None for the corpus' own pairs.  The noise of every row is drawn by `draw_mix` from `mix_rng(seed, epoch,
+    rank)` -- order and crop starts are those of the same loader without remix -- and every gather, redraw passes (which draw a fresh
+    noise tuple) included, is one se_crop_gather_mix.  The key of a mixed row is (file, start, noise file, noise start, snr dB); a
+    row the kernel did not mix (silent noise or speech) keeps the plain (file, start), as do the rows that were not drawn."""
+
+    def __init__(self, dataset, batch_size, crop_samples, shuffle, seed=0, rank=0, world=1, reject=None, remix=None):
         if batch_size < 1 or crop_samples < 1 or not 0 <= rank < world:
             raise ValueError(f'bad loader geometry: batch {batch_size}, crop {crop_samples}, rank {rank} of {world}')
         self.dataset, self.batch_size, self.crop_samples, self.shuffle = dataset, int(batch_size), int(crop_samples), bool(shuffle)
         self.seed, self.rank, self.world, self.epoch = int(seed), int(rank), int(world), 0
         self.reject = reject if reject is not None else zero_energy
-        self._pinned = []
+        if remix is not None and not isinstance(remix, Remix):
+            raise TypeError(f'remix takes a Remix or None (got {type(remix).__name__})')
+        self.remix = remix
+        self._pinned, self._pinned_mix = [], []
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -353,6 +464,36 @@ class DeviceLoader:
         g.pool = self._pinned
         return g
 
+    def _gather_mix(self, files, starts, mix):
+        """launch one se_crop_gather_mix for rows (file, start) with the noise `mix` of draw_mix -> _GatheredMix"""
+        ds, b, Lc = self.dataset, len(files), self.crop_samples
+        rows = np.empty((b, 6), dtype=np.int64)
+        for r, (f, s, m) in enumerate(zip(files, starts, mix)):
+            n = ds.lengths[f]
+            if not (0 <= f < len(ds.lengths)) or (n >= Lc and not 0 <= s <= n - Lc):
+                raise L.SeHipError(f'crop ({f}, {s}) is outside utterance {f} of {n} samples')
+            if m is None:
+                rows[r] = (ds.offsets[f], n, max(s, 0), -1, 0, 0)
+                continue
+            j, sj, _ = m
+            nj = ds.lengths[j]
+            if not (0 <= j < len(ds.lengths)) or (nj >= Lc and not 0 <= sj <= nj - Lc):
+                raise L.SeHipError(f'noise crop ({j}, {sj}) is outside utterance {j} of {nj} samples')
+            rows[r] = (ds.offsets[f], n, max(s, 0), ds.offsets[j], nj, max(sj, 0))
+        g = _GatheredMix()
+        g.chunks = mix_chunks(Lc)
+        g.clean, g.noisy, tail = _launch_mix(ds, rows, [m[2] if m is not None else 0.0 for m in mix], Lc)
+        per = 3 * g.chunks
+        with torch.cuda.device(ds.clean.device):
+            full = self._pinned_mix.pop() if self._pinned_mix else \
+                torch.empty(self.batch_size * per + (self.batch_size + 1) // 2, dtype=torch.float64, pin_memory=True)
+            g.full, g.host = full, full[:tail.numel()]
+            g.host.copy_(tail, non_blocking=True)
+            g.event = torch.cuda.Event()
+            g.event.record()
+        g.pool = self._pinned_mix
+        return g
+
     def _place(self, g, rows, sub):
         """rows `rows` of batch g <- the redrawn crops `sub`"""
         at = torch.as_tensor(rows, device=g.clean.device)
@@ -363,10 +504,12 @@ class DeviceLoader:
         at = torch.as_tensor(keep, device=g.clean.device)
         return g.clean.index_select(0, at), g.noisy.index_select(0, at)
 
-    def _finish(self, files, starts, g, rng):
+    def _finish(self, files, starts, g, rng, mix=None, mrng=None):
         """wait for the statistics of a gathered batch, redraw / drop what they reject -> the item, or None"""
         starts = list(starts)
         bad = np.flatnonzero(np.asarray(self.reject(g.stats()), dtype=bool)).tolist()
+        if mix is not None:
+            mix, scale = list(mix), g.scale
         attempt = 1
         Lc, lengths = self.crop_samples, self.dataset.lengths
         dropped = [r for r in bad if lengths[files[r]] < Lc]
@@ -374,11 +517,18 @@ class DeviceLoader:
         while bad and attempt < MAX_ATTEMPTS:
             sub_files = [files[r] for r in bad]
             sub_starts = self._draw(sub_files, rng)
-            sub = self._gather(sub_files, sub_starts)
+            if mix is None:
+                sub = self._gather(sub_files, sub_starts)
+            else:
+                sub_mix = draw_mix(sub_files, lengths, Lc, mrng, self.remix)
+                sub = self._gather_mix(sub_files, sub_starts, sub_mix)
             self._place(g, bad, sub)
             for r, s in zip(bad, sub_starts):
                 starts[r] = s
             still = np.asarray(self.reject(sub.stats()), dtype=bool)
+            if mix is not None:
+                for k, r in enumerate(bad):
+                    mix[r], scale[r] = sub_mix[k], sub.scale[k]
             bad = [r for r, x in zip(bad, still) if x]
             attempt += 1
         dropped = set(dropped + bad)
@@ -386,22 +536,31 @@ class DeviceLoader:
         if not keep:
             return None
         clean, noisy = (g.clean, g.noisy) if not dropped else self._select(g, keep)
-        return {'audio': clean, 'noisy': noisy, 'keys': [(int(files[r]), int(starts[r])) for r in keep]}
+        keys = [(int(files[r]), int(starts[r])) for r in keep]
+        if mix is not None:
+            keys = [k + (int(mix[r][0]), int(mix[r][1]), float(mix[r][2])) if mix[r] is not None and scale[r] != 0 else k
+                    for k, r in zip(keys, keep)]
+        return {'audio': clean, 'noisy': noisy, 'keys': keys}
 
     def __iter__(self):
         rng = crop_rng(self.seed, self.epoch, self.rank)
+        mrng = mix_rng(self.seed, self.epoch, self.rank) if self.remix is not None else None
         order = self.indices()
         pending = None
         for i in range(0, len(order), self.batch_size):
             files = order[i:i + self.batch_size]
             starts = self._draw(files, rng)
-            cur = (files, starts, self._gather(files, starts))
+            if mrng is None:
+                cur = (files, starts, self._gather(files, starts), rng)
+            else:
+                mix = draw_mix(files, self.dataset.lengths, self.crop_samples, mrng, self.remix)
+                cur = (files, starts, self._gather_mix(files, starts, mix), rng, mix, mrng)
             if pending is not None:
-                item = self._finish(*pending, rng)
+                item = self._finish(*pending)
                 if item is not None:
                     yield item
             pending = cur
         if pending is not None:
-            item = self._finish(*pending, rng)
+            item = self._finish(*pending)
             if item is not None:
                 yield item

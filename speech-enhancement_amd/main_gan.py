@@ -7,7 +7,9 @@ One process per GPU: launch N processes with torch.distributed.run (env:// rende
 spawns them itself like the reference.  With `--synthetic N` the loaders are N synthetic batches per epoch with PESQ labels
 supplied (the bench's data recipe); else `speech_enhancement_amd.main_gan.DATASET_FACTORY`, when set, is a callable returning
 (train, valid) loaders; else the four `config.DATA.*_DIR` wav folders become device-resident datasets (data.py: decoded once,
-resampled to 16 kHz on the GPU, one launch per batch of crops) and the PESQ labels come from the provider (train.py).
+resampled to 16 kHz on the GPU, one launch per batch of crops) and the PESQ labels come from the provider (train.py);
+`--remix-prob P --remix-snr LO HI` then gives a training crop, with probability P, the noise of another utterance at an SNR
+drawn from [LO, HI] dB (data.Remix).
 """
 import argparse
 import os
@@ -62,6 +64,10 @@ def parse_option(argv=None):
     p.add_argument('--comp-type', default='pow', type=str, choices=['norm', 'log', 'pow', 'none'])
     p.add_argument('--synthetic', default=0, type=int, metavar='N',
                    help='train on N synthetic batches per epoch (labels supplied) instead of VoiceBank-DEMAND')
+    p.add_argument('--remix-prob', default=0.0, type=float, metavar='P',
+                   help='wav folders only: probability that a training crop gets the noise of another utterance (data.Remix)')
+    p.add_argument('--remix-snr', default=[0.0, 20.0], type=float, nargs=2, metavar=('LO', 'HI'),
+                   help='SNR range in dB of the remixed training crops')
     args, _ = p.parse_known_args(argv)
     if args.arch == 'diffuse':      # the reference's default is not in its own choices and selects the cmgan branch
         args.arch = 'cmgan'
@@ -89,7 +95,9 @@ def device_loaders(args, config, samples):
     train_set = data.DeviceDataset(config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR, config.SAMPLE_RATE, device=dev)
     valid_set = data.DeviceDataset(config.DATA.TEST_CLEAN_DIR, config.DATA.TEST_NOISY_DIR, config.SAMPLE_RATE, device=dev)
     print('Audio signals cropped to {} seconds long'.format(config.CROP_LEN))
-    train_loader = data.DeviceLoader(train_set, args.batch_size, samples, shuffle=True, rank=rank, world=world)
+    # the training crops only: validation always sees the corpus' own pairs
+    remix = {'remix': data.Remix(args.remix_prob, tuple(args.remix_snr))} if args.remix_prob != 0 else {}
+    train_loader = data.DeviceLoader(train_set, args.batch_size, samples, shuffle=True, rank=rank, world=world, **remix)
     valid_loader = data.DeviceLoader(valid_set, args.batch_size, samples, shuffle=args.distributed, rank=rank, world=world)
     return train_loader, valid_loader
 
@@ -175,6 +183,9 @@ def main_worker(gpu, ngpus_per_node, args, config):
 
 def main(argv=None):
     args, config = parse_option(argv)
+    if args.remix_prob != 0 and (args.synthetic or DATASET_FACTORY is not None):
+        raise RuntimeError('--remix-prob mixes the noise of the device-resident wav folders (config.DATA.*_DIR): it cannot be '
+                           'combined with --synthetic or a DATASET_FACTORY')
     if args.seed is not None:
         random.seed(args.seed)
         torch.manual_seed(args.seed)

@@ -1,10 +1,12 @@
 """Times the dataset layer (speech-enhancement_amd/data.py) on the GPU: building a DeviceDataset from a generated directory of
-48 kHz wavs (decode + upload + resample), the resampling kernel alone, and one DeviceLoader batch.
+48 kHz wavs (decode + upload + resample), the resampling kernel alone, and one DeviceLoader batch -- plain, and with every row
+remixed (data.Remix(1.0): the two launches of se_crop_gather_mix instead of the one of se_crop_gather).
 
     python tools/bench_data.py [--out profiles/data_loader.json] [--files 64] [--seconds 3.0] [--reps 50]
 
 Host clock around work that ends in a device synchronise, after warm-up; median and spread over --reps calls.  One JSON line on
-stdout, the same record in --out."""
+stdout, the same record in --out.  The *_device keys are HIP-event times of 20 back-to-back gathers divided by 20: the launches
+without the host's share (row table upload, statistics download, synchronise)."""
 import argparse
 import json
 import os
@@ -32,6 +34,25 @@ def timed(fn, reps, warmup=5):
         ts.append((time.perf_counter() - t0) * 1e3)
     ts = np.array(ts)
     return {'median_ms': float(np.median(ts)), 'min_ms': float(ts.min()), 'p90_ms': float(np.percentile(ts, 90)), 'reps': reps}
+
+
+def device_timed(fn, reps, burst=20):
+    """fn enqueues one gather; events around `burst` of them, so that the event overhead is shared"""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(burst):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1) / burst)
+    ts = np.array(ts)
+    return {'median_ms': float(np.median(ts)), 'min_ms': float(ts.min()), 'p90_ms': float(np.percentile(ts, 90)), 'reps': reps,
+            'burst': burst}
 
 
 def write_corpus(root, files, seconds, sr, seed):
@@ -119,6 +140,36 @@ def main():
                                       'batches_per_epoch': len(ld), 'reps': args.reps}
     files, starts = list(range(16)), [1000 * i for i in range(16)]
     res['crop_gather_launch_B16_L32000'] = timed(lambda: ld._gather(files, starts).stats(), args.reps)
+    # the same point with every row remixed: noise of the next utterance at 10 dB
+    mix = [((f + 1) % 64, 500 * i, 10.0) for i, f in enumerate(files)]
+    lm = data.DeviceLoader(ds, 16, 32000, shuffle=True, remix=data.Remix(1.0, (0.0, 20.0)))
+    res['crop_gather_mix_launch_B16_L32000'] = timed(lambda: lm._gather_mix(files, starts, mix).stats(), args.reps)
+
+    def one_epoch_mix():
+        epoch[0] += 1
+        lm.set_epoch(epoch[0])
+        for _ in lm:
+            pass
+    r = timed(one_epoch_mix, args.reps)
+    res['loader_batch_remix_B16_L32000'] = {'ms_per_batch_median': r['median_ms'] / len(lm), 'ms_per_batch_min': r['min_ms'] / len(lm),
+                                            'batches_per_epoch': len(lm), 'reps': args.reps}
+    rows = np.array([[ds.offsets[f], ds.lengths[f], s, ds.offsets[m[0]], ds.lengths[m[0]], m[1]]
+                     for f, s, m in zip(files, starts, mix)], dtype=np.int64)
+    rows_d = torch.from_numpy(np.ascontiguousarray(rows[:, :3])).cuda()
+    oc, on, st = torch.empty(16, 32000, device='cuda'), torch.empty(16, 32000, device='cuda'), torch.empty(16, 3, device='cuda')
+    from speech_enhancement_amd import _lib
+    import ctypes as C
+    res['crop_gather_B16_L32000_device'] = device_timed(
+        lambda: _lib.call('se_crop_gather', _lib.ptr(ds.clean), _lib.ptr(ds.noisy), C.c_longlong(ds.clean.numel()), _lib.ptr(rows_d),
+                          C.c_int(16), C.c_int(32000), _lib.ptr(oc), _lib.ptr(on), _lib.ptr(st), _lib.stream()), args.reps)
+    n = data.mix_chunks(32000)
+    table = torch.from_numpy(rows.reshape(-1)).cuda()
+    gain = torch.full((16,), 10.0 ** -0.5, dtype=torch.float64, device='cuda')
+    buf = torch.empty(16 * n * 5 + 8, dtype=torch.float64, device='cuda')
+    res['crop_gather_mix_B16_L32000_device'] = device_timed(
+        lambda: _lib.call('se_crop_gather_mix', _lib.ptr(ds.clean), _lib.ptr(ds.noisy), ds.clean.numel(), _lib.ptr(table),
+                          _lib.ptr(gain), 16, 32000, _lib.ptr(oc), _lib.ptr(on), _lib.ptr(buf[32 * n:]), _lib.ptr(buf[80 * n:]),
+                          _lib.ptr(buf), 16 * n * 16, _lib.stream()), args.reps)
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
