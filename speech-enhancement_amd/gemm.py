@@ -1,5 +1,6 @@
 """Python side of the tap-GEMM family (csrc/se_gemm.hip): descriptors, weight packing, launches."""
 import ctypes as C
+import os
 
 import torch
 
@@ -45,8 +46,8 @@ def make_desc(B, To, Fo, Ti, Fi, taps, C_in, lda, N, ldc, a_off=0, c_off=0, ldw=
 # known (pre-split fp16 weight planes from the step's WeightPlan; LayerNorm outputs with a static exponent; gradients with the
 # maximum their producer measured): fp32-equivalent like bf16x6 at half the MFMAs.  Calls without those scales (plain fp32
 # weights, e.g. direct layer calls in tests) run the six-product kernels.
-LINEAR_PRECISION = {'f32': 0, 'bf16x3': 1, 'bf16x6': 2, 'f16x3': 3}[__import__('os').environ.get('SE_LINEAR_PRECISION', 'f16x3')]
-WGRAD_LINEAR_PRECISION = {'f32': 0, 'bf16x3': 2, 'bf16x6': 2, 'f16x3': 3}[__import__('os').environ.get('SE_WGRAD_PRECISION', 'f16x3')]      # (token-wise weight gradients: the convolutions' switch)
+LINEAR_PRECISION = {'f32': 0, 'bf16x3': 1, 'bf16x6': 2, 'f16x3': 3}[os.environ.get('SE_LINEAR_PRECISION', 'f16x3')]
+WGRAD_LINEAR_PRECISION = {'f32': 0, 'bf16x3': 2, 'bf16x6': 2, 'f16x3': 3}[os.environ.get('SE_WGRAD_PRECISION', 'f16x3')]      # (token-wise weight gradients: the convolutions' switch)
 LN_SEXP = 6        # LayerNorm(64) outputs: |x| <= 7.94 |gamma| + |beta|; 2^6 keeps |x| < 1023 below the fp16 maximum
 HID_SEXP = 3       # Swish(H) * dropout mask (FF hidden activations): |x| < 8191
 
@@ -104,7 +105,7 @@ class _LeafStream:
     reads are kept referenced until the join, so that the main stream cannot recycle their memory early.  (record_stream would
     do the same without extending lifetimes, but blocks freed with a pending cross-stream event are not reusable until the
     lagging leaf stream has passed them: the caching allocator then reserved 150 GB for a 32 GB working set.)"""
-    enabled = __import__('os').environ.get('SE_NO_WGRAD_STREAM') != '1'
+    enabled = os.environ.get('SE_NO_WGRAD_STREAM') != '1'
     active = False
     streams = {}
     keep = []
@@ -150,7 +151,7 @@ class branch_stream:
     main stream after `join()`, and the branch stream re-uses a freed block only after its next entry event, i.e. after every
     main-stream reader queued so far.  The inputs must stay referenced until `join()` (they do: locals of the caller).
     SE_NO_BRANCH_STREAM=1: the branch runs inline."""
-    enabled = __import__('os').environ.get('SE_NO_BRANCH_STREAM') != '1'
+    enabled = os.environ.get('SE_NO_BRANCH_STREAM') != '1'
     streams = {}
 
     def __init__(self, *tensors):
@@ -231,7 +232,7 @@ def gemm_tap_wgrad(d, A, dY, dW, dbias=None, rowstats=None, ps=None, pb=None, ch
     return dW
 
 
-_KEY_SHAPES = __import__('os').environ.get('SE_KEY_SHAPES') == '1'      # diagnostic: one timer family per GEMM shape
+_KEY_SHAPES = os.environ.get('SE_KEY_SHAPES') == '1'      # diagnostic: one timer family per GEMM shape
 
 
 _WGRAD_ARITH = {0: 'f32', 1: 'bf16x3', 2: 'bf16x6', 3: 'f16x3'}
@@ -277,7 +278,7 @@ def gemm_ln_bwd(A, WT, x, stats, gamma, dR, dgamma, dbeta, out_amax=None):
 
 # the LayerNorm-backward GEMM and the weight gradient of the same layer in one sweep over the rows (csrc/se_lnbwd_fused.hip);
 # SE_LNBWD_FUSED=0: two launches again (se_gemm_ln_bwd_f16 + se_gemm_tap_wgrad on the weight-gradient stream)
-LNBWD_FUSED = __import__('os').environ.get('SE_LNBWD_FUSED', '1') != '0'
+LNBWD_FUSED = os.environ.get('SE_LNBWD_FUSED', '1') != '0'
 
 
 def gemm_ln_bwd_wgrad(A, WT, x, stats, gamma, beta, dR, dgamma, dbeta, dW, dbias=None, out_amax=None, in_bound=None):
@@ -363,7 +364,7 @@ def ff_fwd(x, rowstats, gamma, beta, W1, b1, W2, b2, drop_p=0.0, seed_h=0, seed_
 # The fused backward (csrc/se_ff_fused.hip; default with scaled fp16 planes): ONE persistent launch for dX, dgamma / dbeta AND the four
 # weight gradients of the module -- H, S and dZ exist on chip only.  SE_FF_FUSED=0: the stored-H kernels (the forward writes H,
 # ff_bwd_dgrad + two whole-gradient launches) -- the cross-check path of the fused kernels.
-FF_FUSED = __import__('os').environ.get('SE_FF_FUSED', '1') != '0'
+FF_FUSED = os.environ.get('SE_FF_FUSED', '1') != '0'
 
 
 def ff_bwd_fused(dy, x, st, gamma, beta, W1, b1, W2T_scaled, dW1, db1, dW2, db2, dgamma, dbeta, drop_p=0.0, seed_h=0, seed_o=0,

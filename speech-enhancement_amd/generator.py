@@ -78,8 +78,12 @@ def _sp_conv(ch):
 
 
 class _TSCNetFn(torch.autograd.Function):
+    """the generator as one autograd node: forward / backward are the hand-written walk of layers.py.  nin, d: None for the CMGAN
+    generator; the planes of the conditioning spectrum and the projected step embedding [1 or B, 64] for the TSC-diffusion hybrid
+    (plain torch autograd produces d and receives its gradient)."""
+
     @staticmethod
-    def forward(ctx, model, xin, *params):
+    def forward(ctx, model, xin, nin, d, *params):
         P = dict(zip(model._pnames, params))
         P.update(model._buffer_dict())
         train = model.training
@@ -89,7 +93,8 @@ class _TSCNetFn(torch.autograd.Function):
             seed = (torch.initial_seed() * 2654435761 + model._drop_calls * 40503) & 0xFFFFFFFF
             est, c = LY.tscnet_fwd(P, xin.contiguous(), train=train, dp=model.dp,
                                    buffers=model._buffer_dict() if train else None,
-                                   drop=(model.ff_dropout, model.attn_dropout), seed=seed)
+                                   drop=(model.ff_dropout, model.attn_dropout), seed=seed,
+                                   cond=None if nin is None else (nin.contiguous(), d.detach()))
         ctx.c, ctx.P, ctx.model = c, P, model
         return est
 
@@ -104,13 +109,13 @@ class _TSCNetFn(torch.autograd.Function):
             G = {k: (P[k].grad if direct else torch.zeros_like(P[k])) for k in model._pnames}
             LY.GM.leaf_begin()                       # weight gradients on their own stream (gemm.leaf_stream)
             try:
-                LY.tscnet_bwd(P, G, ctx.c, dest.contiguous(), dp=model.dp)
+                dd = LY.tscnet_bwd(P, G, ctx.c, dest.contiguous(), dp=model.dp)
             finally:
                 LY.GM.leaf_join(dest.device)
         ctx.c = None
         if direct:
-            return (None, None) + (None,) * len(model._pnames)
-        return (None, None) + tuple(G[k] for k in model._pnames)
+            return (None, None, None, dd) + (None,) * len(model._pnames)
+        return (None, None, None, dd) + tuple(G[k] for k in model._pnames)
 
 
 class TSCNet(nn.Module):
@@ -177,7 +182,7 @@ class TSCNet(nn.Module):
 
     def forward_planes(self, xin):
         """xin planes [B,T,F,4] -> est planes [B,T,F,4] (|est|, Re, Im, 0); the native entry of the train step."""
-        return _TSCNetFn.apply(self, xin, *[p for _, p in self.named_parameters()])
+        return _TSCNetFn.apply(self, xin, None, None, *[p for _, p in self.named_parameters()])
 
     def forward(self, x, diffusion_step=None):
         xin = FE.spec_to_planes(x)

@@ -7,6 +7,7 @@ adds parameter gradients into ``G`` (dict name -> tensor, fp32, zero-initialised
 Parameter names are the reference's state_dict keys.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -15,13 +16,6 @@ from . import attention as A
 from . import gemm as GM
 from . import ops as O
 
-EPS = 1e-5
-
-# Arithmetic of the MFMA-bound convolution GEMMs (dilated dense stacks, sub-pixel, strided convs): 'f32' = exact
-# fp32 MFMA; 'bf16x6' (default) = every fp32 operand split EXACTLY into three bf16 parts, six bf16 MFMAs per product,
-# fp32 accumulation: fp32-equivalent results (dropped terms <= 2^-24) at 16/6 of the fp32 MFMA rate; 'bf16x3' = two
-# parts / three MFMAs, ~1.5e-5 relative per product (meets the 1e-3 bar with less margin; opt-in).
-import os as _os
 EPS = 1e-5
 
 # Arithmetic of the MFMA-bound convolution GEMMs (dilated dense stacks, sub-pixel, strided convs): 'f32' = exact
@@ -919,42 +913,122 @@ def complex_decoder_bwd(P, G, ctx, dcplx, B, T, Fq):
 
 
 # ------------------------------------------------------------------------------------------------
-# TSCNet (models/generator.py:132-167)
+# MergeBlock of the TSC-diffusion hybrid (models/tsc_diffusion.py:27-40) on tokens [M, 64]
 # ------------------------------------------------------------------------------------------------
-def tscnet_fwd(P, xin, train=True, dp=NO_DP, buffers=None, drop=(0.0, 0.0), seed=0):
+def _merge_weights(P):
+    return (P['merge_block.merge_diffusion.weight'].view(128, 64), P['merge_block.conditioner_projection.weight'].view(128, 64),
+            P['merge_block.output_residual.weight'].view(64, 64))
+
+
+def merge_fwd(P, x, cond, d, B, keep):
+    """y = W_m (x + d) + b_m + W_c cond + b_c;  out = (x + W_r (sigmoid(gate) tanh(filter)) + b_r) / sqrt(2).  d = the projected
+    step embedding, one row per clip or one row for the whole batch.  Per-clip rows are added to x first; ONE step for the whole
+    batch with nothing to keep (predict_tsc, the graphed sampler) folds into the bias (W_m d + b_m, weight-sized).  keep: also
+    return what merge_bwd needs -- the backward reads x + d and returns per-clip gradients, so a single row is then broadcast over
+    the clips instead of folded.  Returns (out, ctx or None)."""
+    M = x.shape[0]
+    Wm, Wc, Wr = _merge_weights(P)
+    bias = P['merge_block.merge_diffusion.bias']
+    if d.shape[0] == 1 and not keep:
+        bias = (bias + (Wm @ d[0])).contiguous()
+        xin = x
+    elif d.shape[0] in (1, B):
+        xin = (x.view(B, -1, 64) + d[:, None, :]).reshape(M, 64)        # per-clip step embedding (plumbing-sized torch add)
+    else:
+        raise L.SeHipError(f'TSCNetDiffusion: diffusion_step must have 1 or {B} entries (got {d.shape[0]})')
+    y = torch.empty(M, 128, device=x.device, dtype=torch.float32)
+    GM.gemm_tap(GM.linear_desc(M, 64, 128, epilogue=L.EPI_BIAS, precision=2), xin, Wm.contiguous(), y, bias=bias)
+    GM.gemm_tap(GM.linear_desc(M, 64, 128, epilogue=L.EPI_BIAS | L.EPI_ACCUM, precision=0), cond, Wc.contiguous(), y,
+                bias=P['merge_block.conditioner_projection.bias'])
+    g = O.gate_tanh(y, M, 64)
+    res = torch.empty(M, 64, device=x.device, dtype=torch.float32)
+    GM.gemm_tap(GM.linear_desc(M, 64, 64, epilogue=L.EPI_BIAS), g, Wr.contiguous(), res, bias=P['merge_block.output_residual.bias'])
+    r2 = 1.0 / math.sqrt(2.0)
+    return O.axpbypcz(x, res, res, r2, r2, 0.0), ((xin, cond, y, g) if keep else None)
+
+
+def merge_bwd(P, G, ctx, dout, B, dcond):
+    """gradients of one MergeBlock application: returns (dx, dd [B, 64]); accumulates into dcond [M, 64] and the shared weights."""
+    xin, cond, y, g = ctx
+    M = dout.shape[0]
+    dev = dout.device
+    Wm, Wc, Wr = _merge_weights(P)
+    r2 = 1.0 / math.sqrt(2.0)
+    dres = O.axpbypcz(dout, dout, dout, r2, 0.0, 0.0)                # d out / d (x + res) = 1 / sqrt(2): dres = dx_direct
+    dg = torch.empty(M, 64, device=dev, dtype=torch.float32)
+    GM.gemm_tap(GM.linear_desc(M, 64, 64), dres, Wr.t().contiguous(), dg)                 # res = g Wr^T  ->  dg = dres Wr
+    dy = O.gate_tanh_bwd(y, dg, M, 64)
+    with GM.leaf_stream(g, dres, xin, cond, dy):
+        GM.gemm_tap_wgrad(GM.linear_desc(M, 64, 64), g, dres, G['merge_block.output_residual.weight'].view(64, 64),
+                          G['merge_block.output_residual.bias'])
+        GM.gemm_tap_wgrad(GM.linear_desc(M, 64, 128), xin, dy, G['merge_block.merge_diffusion.weight'].view(128, 64),
+                          G['merge_block.merge_diffusion.bias'])
+        GM.gemm_tap_wgrad(GM.linear_desc(M, 64, 128), cond, dy, G['merge_block.conditioner_projection.weight'].view(128, 64),
+                          G['merge_block.conditioner_projection.bias'])
+    dx = torch.empty(M, 64, device=dev, dtype=torch.float32)
+    GM.gemm_tap(GM.linear_desc(M, 128, 64, epilogue=L.EPI_RESID, alpha=1.0, ldr=64), dy, Wm.t().contiguous(), dx, R=dres)
+    GM.gemm_tap(GM.linear_desc(M, 128, 64, epilogue=L.EPI_ACCUM), dy, Wc.t().contiguous(), dcond)
+    dd = dy.view(B, -1, 128).sum(1) @ Wm                            # d (x + d): the per-clip column sums of dxin = dy Wm
+    return dx, dd
+
+
+# ------------------------------------------------------------------------------------------------
+# TSCNet (models/generator.py:132-167) and, with a conditioner, the TSC-diffusion hybrid (models/tsc_diffusion.py:43-90)
+# ------------------------------------------------------------------------------------------------
+def tscnet_fwd(P, xin, train=True, dp=NO_DP, buffers=None, drop=(0.0, 0.0), seed=0, cond=None):
     """xin: planes [B, T, F, 4] = (|x|, Re x, Im x, 0) of the compressed noisy spectrum.
+    cond: None (the CMGAN generator) or (nin, d) (the hybrid): nin = planes [B, T, F, 4] of the conditioning spectrum through a
+    second encoder, d = the projected step embedding [1 or B, 64]; a MergeBlock then stands in front of every TSCB.
     returns est planes [B, T, F, 4] = (|est|, Re est, Im est, 0) and the ctx for tscnet_bwd."""
     B, T, Fq, _ = xin.shape
     ctx = {'xin': xin, 'dims': (B, T, Fq)}
+
+    def kept(key, res):
+        # eval mode keeps no block's context (conformer_bwd refuses it, so nothing could consume one): each is freed as the walk goes
+        if train:
+            ctx[key] = res[1]
+        return res[0]
+
     plan = P.get('__prep__')
     if plan is not None:
         # proven bounds of the normalised activations of this forward (LayerNorm outputs, feed-forward hidden activations, train-mode
         # BatchNorm outputs: |x_hat| <= sqrt(tokens over all ranks - 1)) from the current parameters: one launch
         Fp_ = (Fq + 2 - 3) // 2 + 1
         plan.run_bounds(k1=float(max(B * T * Fp_ * dp.world - 1, 1)) ** 0.5)
-    x, ctx['enc'] = encoder_fwd(P, xin, B, T, Fq)
+    x = kept('enc', encoder_fwd(P, xin, B, T, Fq))
     Fp = x.shape[2]
     ctx['Fp'] = Fp
     tok = x.view(B * T * Fp, 64)
+    if cond is not None:
+        nin, d = cond
+        ctok = kept('encn', encoder_fwd(P, nin, B, T, Fq, p='dense_encoder_noisy')).view(B * T * Fp, 64)
+        ctx['merge'] = []
     ctx['tscb'] = []
     st_tok = None                  # row statistics of `tok`, handed from one block's post_norm to the next block's first LayerNorm
     if buffers is not None and train:
         buffers = dict(buffers)
         buffers['_nbt_pending'] = []
     for i in range(1, 5):
+        if cond is not None:
+            tok, cm = merge_fwd(P, tok, ctok, d, B, keep=train)
+            st_tok = None          # (the statistics described the rows the MergeBlock has just changed)
         tok, c1 = conformer_fwd(P, f'TSCB_{i}.time_conformer', tok, B, T, Fp, 'time', train, dp, buffers, drop,
                                 site_seed(seed, 100 + 2 * i), st_in=st_tok)
         st_tok = c1.pop('out_stats', None)
         tok, c2 = conformer_fwd(P, f'TSCB_{i}.freq_conformer', tok, B, T, Fp, 'freq', train, dp, buffers, drop,
                                 site_seed(seed, 101 + 2 * i), st_in=st_tok)
         st_tok = c2.pop('out_stats', None)
-        ctx['tscb'].append((c1, c2))
+        if train:
+            ctx['tscb'].append((c1, c2))
+            if cond is not None:
+                ctx['merge'].append(cm)
+        del c1, c2
     if buffers is not None and buffers.get('_nbt_pending'):
         torch._foreach_add_(buffers['_nbt_pending'], 1)
     # the two decoders are independent branches (models/generator.py:154-156): the complex decoder runs on a second stream
     with GM.branch_stream(tok) as br:
-        cplx, ctx['cplx'] = complex_decoder_fwd(P, tok, B, T, Fp)
-    mask, ctx['mask'] = mask_decoder_fwd(P, tok, B, T, Fp)
+        cplx = kept('cplx', complex_decoder_fwd(P, tok, B, T, Fp))
+    mask = kept('mask', mask_decoder_fwd(P, tok, B, T, Fp))
     br.join()
     est = O.assemble(mask, 1, xin, cplx)
     ctx['est'] = est
@@ -962,7 +1036,8 @@ def tscnet_fwd(P, xin, train=True, dp=NO_DP, buffers=None, drop=(0.0, 0.0), seed
 
 
 def tscnet_bwd(P, G, ctx, dest, dp=NO_DP):
-    """dest: gradient w.r.t. the est planes (dmag, dre, dim, -).  Parameter gradients are added into G."""
+    """dest: gradient w.r.t. the est planes (dmag, dre, dim, -).  Parameter gradients are added into G.
+    Returns None for the generator, the gradient dd [B, 64] of the step embedding (summed over the four MergeBlocks) for the hybrid."""
     B, T, Fq = ctx['dims']
     Fp = ctx['Fp']
     dev = dest.device
@@ -976,10 +1051,20 @@ def tscnet_bwd(P, G, ctx, dest, dp=NO_DP):
     dtok = (dsk_c[..., :64] + dsk_m[..., :64]).reshape(B * T * Fp, 64)      # plumbing: sum of the two decoder branches
     del dsk_c, dsk_m, dcplx
     ctx['cplx'] = ctx['mask'] = None
+    merge = ctx.get('merge')
+    dd = None
+    if merge is not None:
+        dcond = O.zeros(B * T * Fp, 64, device=dev)                         # gradient of the conditioner tokens: four accumulations
     for i in (4, 3, 2, 1):
         c1, c2 = ctx['tscb'][i - 1]
         dtok = conformer_bwd(P, G, f'TSCB_{i}.freq_conformer', c2, dtok, B, T, Fp, dp)
         dtok = conformer_bwd(P, G, f'TSCB_{i}.time_conformer', c1, dtok, B, T, Fp, dp)
         ctx['tscb'][i - 1] = None
+        if merge is not None:
+            dtok, ddi = merge_bwd(P, G, merge[i - 1], dtok, B, dcond)
+            dd = ddi if dd is None else dd + ddi
+            merge[i - 1] = None
     encoder_bwd(P, G, ctx['enc'], dtok.view(B, T, Fp, 64), B, T, Fq)
-    return None
+    if merge is not None:
+        encoder_bwd(P, G, ctx['encn'], dcond.view(B, T, Fp, 64), B, T, Fq, p='dense_encoder_noisy')
+    return dd
