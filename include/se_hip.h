@@ -613,6 +613,19 @@ size_t se_crop_gather_mix_workspace_bytes(int B, int L);
 int se_crop_gather_mix(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows,
                        const double* gain, int B, int L, float* clean, float* noisy, double* stats, float* scale, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* The same gather with the noise taken from a separate arena ("noise bank": bank_total floats, files packed like the corpus) instead
+ * of from the corpus.  rows (device, int64 [B][6]) = (off_s, len_s, start_s, off_n, len_n, start_n): the speech source as above; the
+ * noise source lies in the bank and always wraps,
+ *   d[t] = bank[off_n + (start_n + t) mod len_n]
+ * and is valid iff off_n >= 0, 1 <= len_n <= 2^31 - 1, off_n + len_n <= bank_total and 0 <= start_n < len_n.  Everything else is
+ * the definition of se_crop_gather_mix: Pc, Pd in the same fixed order, a = (float)(sqrt(Pc / Pd) * gain[b]), clean[b][t] = c[t],
+ * noisy[b][t] = fmaf(a, d[t], c[t]), scale[b] = a; off_n < 0 = not mixed; an invalid noise source, Pd == 0, Pc == 0 and an a that is
+ * zero or not finite fall back to noisy_arena at the speech crop with scale[b] = 0; a speech source outside the arena writes zeros;
+ * the same stats, the same workspace (se_crop_gather_mix_workspace_bytes), two launches.  clean_arena == noisy_arena is legal (a
+ * corpus of clean speech alone: an unmixed or fallen-back row then has noisy == clean). */
+int se_crop_gather_bank(const float* clean_arena, const float* noisy_arena, long long arena_total, const float* bank,
+                        long long bank_total, const long long* rows, const double* gain, int B, int L, float* clean, float* noisy,
+                        double* stats, float* scale, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- reverse-diffusion sampler of the TSC hybrid (speech-enhancement_amd/sampler.py; inference_diffuse.py:231-269) ----
  * The step index n (device int32), the utterance counter run (device uint32) and the seed (device uint64) are read on the device,

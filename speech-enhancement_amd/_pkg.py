@@ -17,4 +17,5 @@ from .tsc_diffusion import TSCNetDiffusion, predict_tsc, tsc_diffusion_step, tsc
 from .train import set_pesq_score_provider  # noqa: F401
 from .metrics import compute_metrics, evaluate  # noqa: F401
 from .data import DeviceDataset, DeviceLoader, read_wav, resample  # noqa: F401
+from .data import NoiseBank, BankMix, bank_rng, draw_bank, mix_bank_at_snr  # noqa: F401
 from .sampler import GraphedTSCSampler, sampler_update, philox_normal  # noqa: F401

@@ -161,20 +161,13 @@ extern "C" int se_crop_gather(const float* clean_arena, const float* noisy_arena
   return se_check_launch("se_crop_gather");
 }
 
-// The crop gather with the noise of another utterance mixed in at a drawn SNR (definition: include/se_hip.h).  A row is spread over
+// The crop gather with noise mixed in at a drawn SNR (definition: include/se_hip.h).  A row is spread over
 // nchunk = ceil(L / SE_MIX_CHUNK) workgroups, grid (chunk, row), in two launches: the first leaves every chunk's (sum c^2, sum d^2) in
 // the workspace, the second has every workgroup of a row add that row's partials in index order -- all of them get the same a --
-// and write its chunk.  No atomics, no counters: the launch boundary is the only hand-off.
+// and write its chunk.  No atomics, no counters: the launch boundary is the only hand-off.  Where the noise comes from is a policy
+// of the kernel pair: CorpusNoise = the noise of another utterance of the corpus (se_crop_gather_mix), BankNoise = a file of a
+// separate noise arena, wrapped (se_crop_gather_bank).
 constexpr int MIX_CHUNK = 4096;
-
-struct MixRow {
-  const float* cs;        // clean arena at the speech crop (index i_s(t))
-  const float* vs;        // noisy arena at the speech crop
-  const float* cn;        // clean arena at the noise crop (index i_n(t))
-  const float* vn;        // noisy arena at the noise crop
-  int len_s, len_n;       // tiling periods, 0 = not tiled
-  bool ok, mix;           // the speech source fits the arena; so does the noise source, and the row asks for it
-};
 
 // where a source (offset, length, start) of L samples lies in an arena of `total`: false if it does not fit
 static __device__ __forceinline__ bool mix_source(long long off, long long len, long long start, int L, long long total,
@@ -186,19 +179,83 @@ static __device__ __forceinline__ bool mix_source(long long off, long long len, 
   return off >= 0 && len >= 1 && off <= total && len <= total - off && start >= 0 && (tiled || start <= len - L);
 }
 
-static __device__ __forceinline__ MixRow mix_row(const float* __restrict__ clean_arena, const float* __restrict__ noisy_arena,
-                                                 const long long* __restrict__ rows, int b, int L, long long arena_total) {
+// what the two kernels get besides the row table: the corpus arenas, and the bank (null for CorpusNoise)
+struct MixArenas {
+  const float* clean;
+  const float* noisy;
+  long long total;
+  const float* bank;
+  long long bank_total;
+};
+
+// A noise policy finds its source in a row r = (off_s, len_s, start_s, off_n, len_n, start_n) -- false: the row is not mixed --
+// and hands a thread d[t] for t = t0, t0 + 256, ... after seek(t0).
+struct CorpusNoise {      // d[t] = noisy_arena - clean_arena at the noise crop, with the index rule of the speech source
+  const float* cn;
+  const float* vn;
+  int len_n;              // tiling period, 0 = not tiled
+  __device__ __forceinline__ bool find(const MixArenas& A, const long long* r, int L) {
+    long long fn = 0;
+    len_n = 0;
+    const bool ok = r[3] >= 0 && mix_source(r[3], r[4], r[5], L, A.total, &fn, &len_n);
+    if (!ok) fn = 0;                                    // never dereferenced then; keeps the pointers inside the arena anyway
+    cn = A.clean + fn;
+    vn = A.noisy + fn;
+    return ok;
+  }
+  __device__ __forceinline__ void seek(int) {}
+  __device__ __forceinline__ float next(int t) {
+    const int in = len_n ? t % len_n : t;
+    return vn[in] - cn[in];
+  }
+};
+
+struct BankNoise {        // d[t] = bank[off_n + (start_n + t) mod len_n]: the index is reduced once per thread, then advanced
+  const float* src;
+  unsigned len_n, pos, step;
+  __device__ __forceinline__ bool find(const MixArenas& A, const long long* r, int) {
+    const long long off = r[3], len = r[4], start = r[5];
+    const bool ok = off >= 0 && len >= 1 && len <= 0x7fffffffLL && off <= A.bank_total && len <= A.bank_total - off && start >= 0 &&
+                    start < len;
+    src = A.bank + (ok ? off : 0);                      // never dereferenced when not ok
+    len_n = ok ? (unsigned)len : 1u;
+    pos = ok ? (unsigned)start : 0u;
+    step = (unsigned)CG_THREADS < len_n ? (unsigned)CG_THREADS : (unsigned)CG_THREADS % len_n;
+    return ok;
+  }
+  // start_n < 2^31 - 1 and t0 < 2^30 + SE_MIX_CHUNK: the sum fits 32 bits, and so does pos + step (both below len_n < 2^31).
+  // A file much longer than the crop -- the usual noise recording -- is rarely left: most waves skip the division.
+  __device__ __forceinline__ void seek(int t0) {
+    pos += (unsigned)t0;
+    if (pos >= len_n) pos %= len_n;
+  }
+  __device__ __forceinline__ float next(int) {
+    const float d = src[pos];
+    pos += step;
+    if (pos >= len_n) pos -= len_n;
+    return d;
+  }
+};
+
+template <typename Noise>
+struct MixRow {
+  const float* cs;        // clean arena at the speech crop (index i_s(t))
+  const float* vs;        // noisy arena at the speech crop
+  Noise noise;
+  int len_s;              // tiling period of the speech, 0 = not tiled
+  bool ok, mix;           // the speech source fits the arena; so does the noise source, and the row asks for it
+};
+
+template <typename Noise>
+static __device__ __forceinline__ MixRow<Noise> mix_row(const MixArenas& A, const long long* __restrict__ rows, int b, int L) {
   const long long* r = rows + 6 * (size_t)b;
-  MixRow m;
-  long long fs = 0, fn = 0;
-  m.ok = mix_source(r[0], r[1], r[2], L, arena_total, &fs, &m.len_s);
-  m.mix = m.ok && r[3] >= 0 && mix_source(r[3], r[4], r[5], L, arena_total, &fn, &m.len_n);
+  MixRow<Noise> m;
+  long long fs = 0;
+  m.ok = mix_source(r[0], r[1], r[2], L, A.total, &fs, &m.len_s);
+  m.mix = m.noise.find(A, r, L) && m.ok;
   if (!m.ok) fs = 0;
-  if (!m.mix) fn = 0;                                   // never dereferenced then; keeps the pointers inside the arena anyway
-  m.cs = clean_arena + fs;
-  m.vs = noisy_arena + fs;
-  m.cn = clean_arena + fn;
-  m.vn = noisy_arena + fn;
+  m.cs = A.clean + fs;
+  m.vs = A.noisy + fs;
   return m;
 }
 
@@ -221,21 +278,26 @@ static __device__ __forceinline__ void mix_block_sum(double& x, double& y, doubl
   }
 }
 
+template <typename Noise>
 __global__ __launch_bounds__(CG_THREADS) void crop_mix_power_kernel(const float* __restrict__ clean_arena,
                                                                     const float* __restrict__ noisy_arena,
+                                                                    const float* __restrict__ bank, long long bank_total,
                                                                     const long long* __restrict__ rows, int L, long long arena_total,
                                                                     double* __restrict__ part) {
   __shared__ double red[2][CG_THREADS / 64];
   const int b = blockIdx.y, k = blockIdx.x, nchunk = gridDim.x;
-  const MixRow m = mix_row(clean_arena, noisy_arena, rows, b, L, arena_total);
+  const MixArenas A = {clean_arena, noisy_arena, arena_total, bank, bank_total};
+  MixRow<Noise> m = mix_row<Noise>(A, rows, b, L);
+  const int t0 = k * MIX_CHUNK + threadIdx.x;
   const int t1 = (int)min((long long)L, (long long)(k + 1) * MIX_CHUNK);
   double pc = 0.0, pd = 0.0;
   if (m.mix) {
+    m.noise.seek(t0);
 #pragma unroll 4
-    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) {
-      const int is = m.len_s ? t % m.len_s : t, in = m.len_n ? t % m.len_n : t;
+    for (int t = t0; t < t1; t += CG_THREADS) {
+      const int is = m.len_s ? t % m.len_s : t;
       const float c = m.cs[is];
-      const float d = m.vn[in] - m.cn[in];
+      const float d = m.noise.next(t);
       pc += (double)c * c;
       pd += (double)d * d;
     }
@@ -248,8 +310,10 @@ __global__ __launch_bounds__(CG_THREADS) void crop_mix_power_kernel(const float*
   }
 }
 
+template <typename Noise>
 __global__ __launch_bounds__(CG_THREADS) void crop_mix_write_kernel(const float* __restrict__ clean_arena,
                                                                     const float* __restrict__ noisy_arena,
+                                                                    const float* __restrict__ bank, long long bank_total,
                                                                     const long long* __restrict__ rows,
                                                                     const double* __restrict__ gain, int L, long long arena_total,
                                                                     const double* __restrict__ part, float* __restrict__ clean,
@@ -258,7 +322,8 @@ __global__ __launch_bounds__(CG_THREADS) void crop_mix_write_kernel(const float*
   __shared__ double red[2][CG_THREADS / 64];
   __shared__ float redm[CG_THREADS / 64];
   const int b = blockIdx.y, k = blockIdx.x, nchunk = gridDim.x;
-  const MixRow m = mix_row(clean_arena, noisy_arena, rows, b, L, arena_total);
+  const MixArenas A = {clean_arena, noisy_arena, arena_total, bank, bank_total};
+  MixRow<Noise> m = mix_row<Noise>(A, rows, b, L);
   // every workgroup of the row adds the same partials in the same order: one a per row without a word passed between them
   float a = 0.f;
   if (m.mix) {
@@ -272,19 +337,21 @@ __global__ __launch_bounds__(CG_THREADS) void crop_mix_write_kernel(const float*
     if (!isfinite(a)) a = 0.f;
   }
   const bool mix = a != 0.f;
+  const int t0 = k * MIX_CHUNK + threadIdx.x;
   const int t1 = (int)min((long long)L, (long long)(k + 1) * MIX_CHUNK);
   float* co = clean + (size_t)b * L;
   float* no = noisy + (size_t)b * L;
   double sc = 0.0, sn = 0.0;
   float mx = 0.f;
   if (!m.ok) {                                          // a speech source outside the arena: silence, which the loader rejects
-    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) co[t] = no[t] = 0.f;
+    for (int t = t0; t < t1; t += CG_THREADS) co[t] = no[t] = 0.f;
   } else if (mix) {
+    m.noise.seek(t0);
 #pragma unroll 4
-    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) {
-      const int is = m.len_s ? t % m.len_s : t, in = m.len_n ? t % m.len_n : t;
+    for (int t = t0; t < t1; t += CG_THREADS) {
+      const int is = m.len_s ? t % m.len_s : t;
       const float c = m.cs[is];
-      const float d = m.vn[in] - m.cn[in];
+      const float d = m.noise.next(t);
       const float v = fmaf(a, d, c);
       co[t] = c;
       no[t] = v;
@@ -294,7 +361,7 @@ __global__ __launch_bounds__(CG_THREADS) void crop_mix_write_kernel(const float*
     }
   } else {                                              // unmixed, or fallen back: what crop_gather_kernel writes
 #pragma unroll 4
-    for (int t = k * MIX_CHUNK + threadIdx.x; t < t1; t += CG_THREADS) {
+    for (int t = t0; t < t1; t += CG_THREADS) {
       const int is = m.len_s ? t % m.len_s : t;
       const float c = m.cs[is], v = m.vs[is];
       co[t] = c;
@@ -322,6 +389,18 @@ extern "C" size_t se_crop_gather_mix_workspace_bytes(int B, int L) {
   return (size_t)B * (size_t)cdiv(L, MIX_CHUNK) * 2 * sizeof(double);
 }
 
+template <typename Noise>
+static void launch_crop_mix(const float* clean_arena, const float* noisy_arena, long long arena_total, const float* bank,
+                            long long bank_total, const long long* rows, const double* gain, int B, int L, float* clean, float* noisy,
+                            double* stats, float* scale, void* workspace, void* stream) {
+  const dim3 grid(cdiv(L, MIX_CHUNK), B);
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(crop_mix_power_kernel<Noise>, grid, dim3(CG_THREADS), 0, as_stream(stream), clean_arena, noisy_arena, bank,
+                     bank_total, rows, L, arena_total, part);
+  hipLaunchKernelGGL(crop_mix_write_kernel<Noise>, grid, dim3(CG_THREADS), 0, as_stream(stream), clean_arena, noisy_arena, bank,
+                     bank_total, rows, gain, L, arena_total, part, clean, noisy, stats, scale);
+}
+
 extern "C" int se_crop_gather_mix(const float* clean_arena, const float* noisy_arena, long long arena_total, const long long* rows,
                                   const double* gain, int B, int L, float* clean, float* noisy, double* stats, float* scale,
                                   void* workspace, size_t workspace_bytes, void* stream) {
@@ -334,11 +413,22 @@ extern "C" int se_crop_gather_mix(const float* clean_arena, const float* noisy_a
   SE_REQUIRE(workspace_bytes >= se_crop_gather_mix_workspace_bytes(B, L) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
              "crop_gather_mix: the workspace has %zu bytes, %zu are needed (8-byte aligned)", workspace_bytes,
              se_crop_gather_mix_workspace_bytes(B, L));
-  const dim3 grid(cdiv(L, MIX_CHUNK), B);
-  double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(crop_mix_power_kernel, grid, dim3(CG_THREADS), 0, as_stream(stream), clean_arena, noisy_arena, rows, L,
-                     arena_total, part);
-  hipLaunchKernelGGL(crop_mix_write_kernel, grid, dim3(CG_THREADS), 0, as_stream(stream), clean_arena, noisy_arena, rows, gain, L,
-                     arena_total, part, clean, noisy, stats, scale);
+  launch_crop_mix<CorpusNoise>(clean_arena, noisy_arena, arena_total, nullptr, 0, rows, gain, B, L, clean, noisy, stats, scale,
+                               workspace, stream);
   return se_check_launch("se_crop_gather_mix");
+}
+
+extern "C" int se_crop_gather_bank(const float* clean_arena, const float* noisy_arena, long long arena_total, const float* bank,
+                                   long long bank_total, const long long* rows, const double* gain, int B, int L, float* clean,
+                                   float* noisy, double* stats, float* scale, void* workspace, size_t workspace_bytes, void* stream) {
+  SE_REQUIRE(clean_arena && noisy_arena && bank && rows && gain && clean && noisy && stats && scale && workspace,
+             "crop_gather_bank: null operand");
+  SE_REQUIRE(B > 0 && B <= 65535 && L > 0 && L <= (1 << 30) && arena_total > 0 && bank_total > 0,
+             "crop_gather_bank: bad sizes (B %d, L %d, arena %lld, bank %lld)", B, L, arena_total, bank_total);
+  SE_REQUIRE(workspace_bytes >= se_crop_gather_mix_workspace_bytes(B, L) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+             "crop_gather_bank: the workspace has %zu bytes, %zu are needed (8-byte aligned)", workspace_bytes,
+             se_crop_gather_mix_workspace_bytes(B, L));
+  launch_crop_mix<BankNoise>(clean_arena, noisy_arena, arena_total, bank, bank_total, rows, gain, B, L, clean, noisy, stats, scale,
+                             workspace, stream);
+  return se_check_launch("se_crop_gather_bank");
 }

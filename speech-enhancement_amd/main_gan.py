@@ -9,7 +9,8 @@ supplied (the bench's data recipe); else `speech_enhancement_amd.main_gan.DATASE
 (train, valid) loaders; else the four `config.DATA.*_DIR` wav folders become device-resident datasets (data.py: decoded once,
 resampled to 16 kHz on the GPU, one launch per batch of crops) and the PESQ labels come from the provider (train.py);
 `--remix-prob P --remix-snr LO HI` then gives a training crop, with probability P, the noise of another utterance at an SNR
-drawn from [LO, HI] dB (data.Remix).
+drawn from [LO, HI] dB (data.Remix); `--noise-dir DIR [DIR ...] --noise-prob P --noise-snr LO HI` adds noise from folders of
+recordings outside the corpus instead (data.NoiseBank), and with `DATA.TRAIN_NOISY_DIR ''` and P = 1 trains from clean speech alone.
 """
 import argparse
 import os
@@ -68,6 +69,13 @@ def parse_option(argv=None):
                    help='wav folders only: probability that a training crop gets the noise of another utterance (data.Remix)')
     p.add_argument('--remix-snr', default=[0.0, 20.0], type=float, nargs=2, metavar=('LO', 'HI'),
                    help='SNR range in dB of the remixed training crops')
+    p.add_argument('--noise-dir', default=None, type=str, nargs='+', metavar='DIR',
+                   help='wav folders only: folders (searched recursively) of noise recordings mixed into the training crops '
+                        '(data.NoiseBank); with DATA.TRAIN_NOISY_DIR \'\' the training set is clean speech alone')
+    p.add_argument('--noise-prob', default=1.0, type=float, metavar='P',
+                   help='probability that a training crop gets its noise from --noise-dir')
+    p.add_argument('--noise-snr', default=[0.0, 20.0], type=float, nargs=2, metavar=('LO', 'HI'),
+                   help='SNR range in dB of the training crops mixed from --noise-dir')
     args, _ = p.parse_known_args(argv)
     if args.arch == 'diffuse':      # the reference's default is not in its own choices and selects the cmgan branch
         args.arch = 'cmgan'
@@ -86,17 +94,35 @@ def synthetic_loader(n_batches, batch, samples, seed):
     return out
 
 
+def check_noise_flags(args, config):
+    """the combinations of --noise-dir that cannot work, and a clean-only training set without its noise"""
+    noise_dir = getattr(args, 'noise_dir', None)
+    if noise_dir and args.remix_prob != 0:
+        raise RuntimeError('--noise-dir takes the noise of the training crops from a noise bank, --remix-prob from the corpus: '
+                           'one loader does one of the two')
+    if not config.DATA.TRAIN_NOISY_DIR and (not noise_dir or getattr(args, 'noise_prob', 1.0) != 1.0):
+        raise RuntimeError("DATA.TRAIN_NOISY_DIR is '': training from clean speech alone takes all its noise from a noise bank, "
+                           'pass --noise-dir DIR [DIR ...] and leave --noise-prob at 1')
+
+
 def device_loaders(args, config, samples):
     """main_gan.py:222-253 on the device (data.py): both corpora resident on this rank's GPU, the per-rank batch size, and the
     reference's sampling -- shuffled when there is no sampler (train) or a DistributedSampler with its defaults (both)"""
     from . import data
     dev = torch.device('cuda', args.gpu)
     rank, world = (args.rank, args.world_size) if args.distributed else (0, 1)
-    train_set = data.DeviceDataset(config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR, config.SAMPLE_RATE, device=dev)
+    noise_dir = getattr(args, 'noise_dir', None)
+    check_noise_flags(args, config)
+    train_set = data.DeviceDataset(config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR or None, config.SAMPLE_RATE, device=dev)
     valid_set = data.DeviceDataset(config.DATA.TEST_CLEAN_DIR, config.DATA.TEST_NOISY_DIR, config.SAMPLE_RATE, device=dev)
     print('Audio signals cropped to {} seconds long'.format(config.CROP_LEN))
     # the training crops only: validation always sees the corpus' own pairs
     remix = {'remix': data.Remix(args.remix_prob, tuple(args.remix_snr))} if args.remix_prob != 0 else {}
+    if noise_dir:                   # each rank holds its own bank, as it holds its own corpus
+        bank = data.NoiseBank(noise_dir, config.SAMPLE_RATE, device=dev)
+        print('Noise bank: {} files, {:.2f} hours, {} bytes resident'.format(len(bank.files), bank.total / config.SAMPLE_RATE / 3600.0,
+                                                                             bank.nbytes))
+        remix = {'bank': data.BankMix(bank, args.noise_prob, tuple(args.noise_snr))}
     train_loader = data.DeviceLoader(train_set, args.batch_size, samples, shuffle=True, rank=rank, world=world, **remix)
     valid_loader = data.DeviceLoader(valid_set, args.batch_size, samples, shuffle=args.distributed, rank=rank, world=world)
     return train_loader, valid_loader
@@ -148,8 +174,8 @@ def main_worker(gpu, ngpus_per_node, args, config):
         valid_loader = train_loader[:1]
     elif DATASET_FACTORY is not None:
         train_loader, valid_loader = DATASET_FACTORY(args, config)
-    elif all(os.path.isdir(d) for d in (config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR, config.DATA.TEST_CLEAN_DIR,
-                                        config.DATA.TEST_NOISY_DIR)):
+    elif all(os.path.isdir(d) for d in (config.DATA.TRAIN_CLEAN_DIR, config.DATA.TRAIN_NOISY_DIR or config.DATA.TRAIN_CLEAN_DIR,
+                                        config.DATA.TEST_CLEAN_DIR, config.DATA.TEST_NOISY_DIR)):
         train_loader, valid_loader = device_loaders(args, config, samples)
     else:
         raise RuntimeError('the VoiceBank dataset / collator is outside this package: pass --synthetic N or set '
@@ -186,6 +212,12 @@ def main(argv=None):
     if args.remix_prob != 0 and (args.synthetic or DATASET_FACTORY is not None):
         raise RuntimeError('--remix-prob mixes the noise of the device-resident wav folders (config.DATA.*_DIR): it cannot be '
                            'combined with --synthetic or a DATASET_FACTORY')
+    if args.synthetic or DATASET_FACTORY is not None:
+        if args.noise_dir:
+            raise RuntimeError('--noise-dir mixes into crops of the device-resident wav folders (config.DATA.*_DIR): it cannot be '
+                               'combined with --synthetic or a DATASET_FACTORY')
+    else:
+        check_noise_flags(args, config)
     if args.seed is not None:
         random.seed(args.seed)
         torch.manual_seed(args.seed)

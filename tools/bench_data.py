@@ -1,6 +1,7 @@
 """Times the dataset layer (speech-enhancement_amd/data.py) on the GPU: building a DeviceDataset from a generated directory of
 48 kHz wavs (decode + upload + resample), the resampling kernel alone, and one DeviceLoader batch -- plain, and with every row
-remixed (data.Remix(1.0): the two launches of se_crop_gather_mix instead of the one of se_crop_gather).
+remixed (data.Remix(1.0): the two launches of se_crop_gather_mix instead of the one of se_crop_gather) or mixed from a resident noise
+bank (data.BankMix(bank, 1.0): se_crop_gather_bank).
 
     python tools/bench_data.py [--out profiles/data_loader.json] [--files 64] [--seconds 3.0] [--reps 50]
 
@@ -89,6 +90,16 @@ class Resident:
         return len(self.lengths)
 
 
+class ResidentBank:
+    """what DeviceLoader needs of a NoiseBank, filled with noise on the device"""
+
+    def __init__(self, files, samples):
+        self.lengths = [samples] * files
+        self.offsets = [samples * i for i in range(files)]
+        self.total = samples * files
+        self.arena = 0.05 * torch.randn(self.total, device='cuda')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'data_loader.json'))
@@ -170,6 +181,22 @@ def main():
         lambda: _lib.call('se_crop_gather_mix', _lib.ptr(ds.clean), _lib.ptr(ds.noisy), ds.clean.numel(), _lib.ptr(table),
                           _lib.ptr(gain), 16, 32000, _lib.ptr(oc), _lib.ptr(on), _lib.ptr(buf[32 * n:]), _lib.ptr(buf[80 * n:]),
                           _lib.ptr(buf), 16 * n * 16, _lib.stream()), args.reps)
+    # the same rows with the noise taken from a bank of 64 x 10 s: file f + 1 from the same starts, which never wrap here
+    bank = ResidentBank(64, 160000)
+    res['crop_gather_bank_B16_L32000_device'] = device_timed(
+        lambda: _lib.call('se_crop_gather_bank', _lib.ptr(ds.clean), _lib.ptr(ds.noisy), ds.clean.numel(), _lib.ptr(bank.arena),
+                          bank.total, _lib.ptr(table), _lib.ptr(gain), 16, 32000, _lib.ptr(oc), _lib.ptr(on), _lib.ptr(buf[32 * n:]),
+                          _lib.ptr(buf[80 * n:]), _lib.ptr(buf), 16 * n * 16, _lib.stream()), args.reps)
+    lb = data.DeviceLoader(ds, 16, 32000, shuffle=True, bank=data.BankMix(bank, 1.0, (0.0, 20.0)))
+
+    def one_epoch_bank():
+        epoch[0] += 1
+        lb.set_epoch(epoch[0])
+        for _ in lb:
+            pass
+    r = timed(one_epoch_bank, args.reps)
+    res['loader_batch_bank_B16_L32000'] = {'ms_per_batch_median': r['median_ms'] / len(lb), 'ms_per_batch_min': r['min_ms'] / len(lb),
+                                           'batches_per_epoch': len(lb), 'reps': args.reps}
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
