@@ -62,6 +62,8 @@ def lib():
                                ('se_sampler_advance', [p, p, i, p, p, p]),
                                ('se_sampler_begin', [p, p, p, p, i, i, i, p]),
                                ('se_philox_normal', [C.c_ulonglong, u, u, C.c_ulonglong, q, p, p, p]),
+                               ('se_diffuse_draw_steps', [C.c_ulonglong, u, u, i, i, p, p]),
+                               ('se_diffuse_noise', [p, p, p, p, p, p, C.c_ulonglong, u, u, i, q, i, p, p, p, p]),
                                ('se_crop_gather_mix', [p, p, q, p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
                                ('se_crop_gather_bank', [p, p, q, p, q, p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
                                ('se_crop_gather_mix_workspace_bytes', [i, i])):

@@ -4,6 +4,9 @@
 //   se_sampler_update   the [B, L] update of one reverse step, the Gaussian noise drawn in the kernel (Philox4x32-10 + Box-Muller)
 //   se_sampler_advance  n -> n - 1 (wrapping to steps - 1 and counting the utterance), d = row n of the step-embedding table
 //   se_philox_normal    the generator alone (tests)
+// and the forward process of its training step with the same generator (speech-enhancement_amd/tsc_diffusion.py):
+//   se_diffuse_draw_steps  one diffusion step per clip
+//   se_diffuse_noise       clip scaling + add_noise of a [B, L] batch in one launch, the noise supplied or drawn in the kernel
 // All of them are HBM-bound and tiny next to the generator they sit behind; the bar is the definition in include/se_hip.h, no scratch,
 // and a draw that depends on (seed, run, n, element) only.
 #include "se_common.h"
@@ -172,6 +175,129 @@ extern "C" int se_sampler_update(float* audio, const float* noisy, const float* 
     hipLaunchKernelGGL(sampler_update_kernel<false>, grid, dim3(SP_THREADS), 0, as_stream(stream), audio, noisy, eps, coef, n, steps,
                        noise, seed, run, c_inv, gamma, clamp, L, total);
   return se_check_launch("se_sampler_update");
+}
+
+// ---- forward process of the hybrid's training step (speech-enhancement_amd/tsc_diffusion.py; core/function.py:25-44, 647-659) ----
+// One Philox call per row: word 0 of counter (b, 0, c2, c3) scaled to [0, steps) in exact integer arithmetic.
+__global__ __launch_bounds__(SP_THREADS) void diffuse_draw_steps_kernel(uint32_t k0, uint32_t k1, uint32_t c2, uint32_t c3, int B,
+                                                                        uint32_t steps, long long* __restrict__ t_out) {
+  const int b = blockIdx.x * SP_THREADS + threadIdx.x;
+  if (b >= B) return;
+  const u32x4_ w = philox4x32_10_({(uint32_t)b, 0u, c2, c3}, k0, k1);
+  t_out[b] = (long long)(((uint64_t)w.x * steps) >> 32);
+}
+
+extern "C" int se_diffuse_draw_steps(unsigned long long seed, unsigned c2, unsigned c3, int B, int steps, long long* t_out,
+                                     void* stream) {
+  SE_REQUIRE(t_out, "diffuse_draw_steps: null output");
+  SE_REQUIRE(B > 0 && steps > 0, "diffuse_draw_steps: bad sizes (B %d, steps %d)", B, steps);
+  hipLaunchKernelGGL(diffuse_draw_steps_kernel, dim3((unsigned)((B + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0,
+                     as_stream(stream), (uint32_t)seed, (uint32_t)(seed >> 32), c2, c3, B, (uint32_t)steps, t_out);
+  return se_check_launch("se_diffuse_draw_steps");
+}
+
+// the five coefficients of a row's diffusion step and its clip scale; a step outside the table selects zeros for the whole row
+struct diffuse_row_ {
+  float cb, A, Bn, S, G, H;
+  bool ok;
+};
+
+static __device__ __forceinline__ diffuse_row_ diffuse_row_load_(const float* __restrict__ c, const float* __restrict__ coef,
+                                                                  const long long* __restrict__ t, int steps, long long b) {
+  diffuse_row_ r = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, false};
+  const long long k = t[b];
+  if (k >= 0 && k < steps) {                              // checked before the table is indexed
+    const float* q = coef + 5 * k;
+    r.cb = c[b], r.A = q[0], r.Bn = q[1], r.S = q[2], r.G = q[3], r.H = q[4];
+    r.ok = true;
+  }
+  return r;
+}
+
+// One thread = one group of four flat elements 4g .. 4g + 3 of the [B, L] tensors, as in sampler_update_kernel: the Philox group is
+// the flat group, so a draw does not depend on L or on the launch, and a group may straddle rows (the row's values are reloaded where
+// the row changes: L may be 1).  VEC: all operands are 16-byte aligned, so every full group is one 16-byte access per tensor.
+template <bool VEC>
+__global__ __launch_bounds__(SP_THREADS) void diffuse_noise_kernel(const float* __restrict__ clean, const float* __restrict__ noisy,
+                                                                   const float* __restrict__ c, const float* __restrict__ coef,
+                                                                   const long long* __restrict__ t, int steps,
+                                                                   const float* __restrict__ noise, uint32_t k0, uint32_t k1,
+                                                                   uint32_t c2, uint32_t c3, long long L, long long total,
+                                                                   float* __restrict__ noisy_n, float* __restrict__ x_t,
+                                                                   float* __restrict__ combine) {
+  const long long g = (long long)blockIdx.x * SP_THREADS + threadIdx.x;
+  const long long i0 = 4 * g;
+  if (i0 >= total) return;
+  const int cnt = (int)(total - i0 < 4 ? total - i0 : 4);
+  const bool full = VEC && cnt == 4;
+  float a[4], y[4], z[4];
+  if (full) {
+    const float4 va = *reinterpret_cast<const float4*>(clean + i0), vy = *reinterpret_cast<const float4*>(noisy + i0);
+    a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
+    y[0] = vy.x, y[1] = vy.y, y[2] = vy.z, y[3] = vy.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool ok = j < cnt;
+      a[j] = ok ? clean[i0 + j] : 0.f;
+      y[j] = ok ? noisy[i0 + j] : 0.f;
+    }
+  }
+  if (noise) {
+    if (full) {
+      const float4 vz = *reinterpret_cast<const float4*>(noise + i0);
+      z[0] = vz.x, z[1] = vz.y, z[2] = vz.z, z[3] = vz.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) z[j] = j < cnt ? noise[i0 + j] : 0.f;
+    }
+  } else {
+    const float4 vz = normals4_(philox4x32_10_({(uint32_t)g, (uint32_t)((uint64_t)g >> 32), c2, c3}, k0, k1));
+    z[0] = vz.x, z[1] = vz.y, z[2] = vz.z, z[3] = vz.w;
+  }
+  long long b = i0 / L, r = i0 - b * L;                   // row and column of element i0; i0 < total, so b < B
+  diffuse_row_ w = diffuse_row_load_(c, coef, t, steps, b);
+  float on[4], ox[4], oc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    // xc, xn: one rounded product each (not contracted into the sums that use them), so noisy_n is torch's noisy * c bit for bit
+    const float xc = __fmul_rn(w.cb, a[j]), xn = __fmul_rn(w.cb, y[j]);
+    on[j] = w.ok ? xn : 0.f;
+    ox[j] = w.ok ? fmaf(w.S, z[j], fmaf(w.Bn, xn, w.A * xc)) : 0.f;
+    oc[j] = w.ok ? fmaf(w.H, z[j], w.G * __fsub_rn(xn, xc)) : 0.f;
+    if (++r == L && j + 1 < cnt) {                        // the next element opens row b + 1 (< B: it is below total)
+      r = 0;
+      w = diffuse_row_load_(c, coef, t, steps, ++b);
+    }
+  }
+  if (full) {
+    *reinterpret_cast<float4*>(noisy_n + i0) = make_float4(on[0], on[1], on[2], on[3]);
+    *reinterpret_cast<float4*>(x_t + i0) = make_float4(ox[0], ox[1], ox[2], ox[3]);
+    *reinterpret_cast<float4*>(combine + i0) = make_float4(oc[0], oc[1], oc[2], oc[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) noisy_n[i0 + j] = on[j], x_t[i0 + j] = ox[j], combine[i0 + j] = oc[j];
+  }
+}
+
+extern "C" int se_diffuse_noise(const float* clean, const float* noisy, const float* c, const float* coef, const long long* t,
+                                const float* noise, unsigned long long seed, unsigned c2, unsigned c3, int B, long long L, int steps,
+                                float* noisy_n, float* x_t, float* combine, void* stream) {
+  SE_REQUIRE(clean && noisy && c && coef && t && noisy_n && x_t && combine, "diffuse_noise: null operand");
+  SE_REQUIRE(B > 0 && L > 0 && steps > 0, "diffuse_noise: bad sizes (B %d, L %lld, steps %d)", B, L, steps);
+  SE_REQUIRE(L <= ((long long)1 << 40) / B, "diffuse_noise: %d x %lld elements are more than one launch covers", B, L);
+  const long long total = (long long)B * L, groups = (total + 3) / 4;
+  const dim3 grid((unsigned)((groups + SP_THREADS - 1) / SP_THREADS));
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(clean) | reinterpret_cast<uintptr_t>(noisy) | reinterpret_cast<uintptr_t>(noise) |
+                         reinterpret_cast<uintptr_t>(noisy_n) | reinterpret_cast<uintptr_t>(x_t) | reinterpret_cast<uintptr_t>(combine);
+  if ((bits & 15) == 0)
+    hipLaunchKernelGGL(diffuse_noise_kernel<true>, grid, dim3(SP_THREADS), 0, as_stream(stream), clean, noisy, c, coef, t, steps, noise,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), c2, c3, L, total, noisy_n, x_t, combine);
+  else
+    hipLaunchKernelGGL(diffuse_noise_kernel<false>, grid, dim3(SP_THREADS), 0, as_stream(stream), clean, noisy, c, coef, t, steps, noise,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), c2, c3, L, total, noisy_n, x_t, combine);
+  return se_check_launch("se_diffuse_noise");
 }
 
 // One workgroup, after the update in stream order: every lane reads n before lane 0 replaces it.

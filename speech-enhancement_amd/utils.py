@@ -11,7 +11,7 @@ def adjust_learning_rate(optimizers, epoch, config):
     """utils/utils.py:78-90: linear warm-up then half-cosine per cycle, peak halved each cycle; written to every
     param group of every optimizer; returns lr + MIN_LR."""
     s = config.TRAIN.SCHEDULER
-    cycle = s.EPOCHS // s.CYCLE_LIMIT
+    cycle = max(s.EPOCHS // s.CYCLE_LIMIT, 1)          # (fewer epochs than cycles divided by zero: one-epoch cycles instead)
     q, r = divmod(epoch, cycle)
     if r < s.WARMUP_EPOCHS:
         lr = 0.5 ** q * s.LR * r / s.WARMUP_EPOCHS

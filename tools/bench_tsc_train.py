@@ -1,15 +1,107 @@
-import sys, time, types, numpy as np, torch
-import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import speech_enhancement_amd as S
-from speech_enhancement_amd import optim
+"""Training step of the TSC-diffusion hybrid at batch 16 x 2 s, device time (HIP events), median and p90:
+  - the prologue alone (everything in front of the two STFTs): eager = clip_scale, two scalings, torch.randint, torch.randn_like and
+    the elementwise passes of add_noise; fused = clip_scale, se_diffuse_draw_steps, se_diffuse_noise;
+  - the whole step with torch's draws (the step as it was before the seeded path existed) and with seed= (the fused prologue),
+    alternating in one run so both see the same machine.
+Writes profiles/tsc_train.json.  There is no bar on the prologue; the seeded step may not exceed the unseeded step's median by more than
+that step's own p90 - median (`seeded_within_spread`)."""
+import json
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import speech_enhancement_amd as S  # noqa: E402
+from speech_enhancement_amd import ops, optim, tsc_diffusion as TD  # noqa: E402
+
 NS = np.linspace(1e-4, 0.035, 50).tolist()
-m = S.TSCNetDiffusion(64, 201, NS); m.apply(S.kaiming_init); m.cuda().train()
-args = types.SimpleNamespace(optimizer='adamw', lr=5e-4, weight_decay=0.01, momentum=0.9, max_norm=0.0)
-opt = optim.build_optimizer(args, m)
-B = 16
-clean = 0.1 * torch.randn(B, 32000, device='cuda'); noisy = clean + 0.05 * torch.randn_like(clean)
-for _ in range(2): l = S.tsc_diffusion_step(m, opt, clean, noisy, NS)
-torch.cuda.synchronize(); t0 = time.time()
-for _ in range(4): l = S.tsc_diffusion_step(m, opt, clean, noisy, NS)
-torch.cuda.synchronize(); dt = (time.time() - t0) / 4
-print(f'TSC-diffusion train step, batch {B} x 2 s: {dt*1e3:.1f} ms/step = {B/dt:.1f} utt/s, loss {float(l):.4f}')
+B, LEN = 16, 32000
+PROLOGUE_REPS, STEP_REPS = 100, 30
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    return e0, e1
+
+
+def stats(events):
+    torch.cuda.synchronize()
+    ms = np.array([a.elapsed_time(b) for a, b in events])
+    return {'median_ms': float(np.median(ms)), 'p90_ms': float(np.percentile(ms, 90)), 'min_ms': float(ms.min()), 'reps': len(ms)}
+
+
+def main():
+    m = S.TSCNetDiffusion(64, 201, NS)
+    m.apply(S.kaiming_init)
+    m.cuda().train()
+    args = types.SimpleNamespace(optimizer='adamw', lr=5e-4, weight_decay=0.01, momentum=0.9, max_norm=0.0)
+    opt = optim.build_optimizer(args, m)
+    clean = 0.1 * torch.randn(B, LEN, device='cuda')
+    noisy = clean + 0.05 * torch.randn_like(clean)
+    coef = TD._coef_table(NS, clean.device)
+
+    def eager_prologue():
+        c = ops.clip_scale(noisy)
+        return TD.add_noise(clean * c[:, None], noisy * c[:, None], NS)
+
+    def fused_prologue(k=[0]):
+        k[0] += 1
+        c = ops.clip_scale(noisy)
+        t = TD.draw_steps(0, k[0], TD.STEP_STREAM, B, len(NS), clean.device)
+        return TD.diffusion_noise(clean, noisy, c, coef, t, seed=0, c2=k[0], c3=0)
+
+    def step_torch():
+        return S.tsc_diffusion_step(m, opt, clean, noisy, NS)
+
+    last = {}
+
+    def step_seeded(k=[0]):
+        k[0] += 1
+        last['loss'] = S.tsc_diffusion_step(m, opt, clean, noisy, NS, seed=0, counter=(k[0], 0))
+
+    for fn in (eager_prologue, fused_prologue):
+        for _ in range(5):
+            fn()
+    ev = {'eager': [], 'fused': []}
+    for _ in range(PROLOGUE_REPS):
+        ev['eager'].append(timed(eager_prologue))
+        ev['fused'].append(timed(fused_prologue))
+    out = {'batch': B, 'samples': LEN, 'timer': 'HIP events on the launch stream, one pair per repetition, the two forms alternating',
+           'prologue_eager': stats(ev['eager']), 'prologue_fused': stats(ev['fused'])}
+    for _ in range(3):
+        step_torch()
+        step_seeded()
+    ev = {'torch': [], 'seeded': []}
+    for _ in range(STEP_REPS):
+        ev['torch'].append(timed(step_torch))
+        ev['seeded'].append(timed(step_seeded))
+    out['step_torch_draws'], out['step_seeded'] = stats(ev['torch']), stats(ev['seeded'])
+    p = out['step_torch_draws']
+    out['allowed_excess_ms'] = p['p90_ms'] - p['median_ms']
+    out['seeded_within_spread'] = bool(out['step_seeded']['median_ms'] <= p['median_ms'] + out['allowed_excess_ms'])
+    out['loss'] = float(last['loss'])
+    for k in ('prologue_eager', 'prologue_fused'):
+        print(f'{k}: median {out[k]["median_ms"]:.3f} ms, p90 {out[k]["p90_ms"]:.3f} ms over {out[k]["reps"]} repetitions')
+    for k in ('step_torch_draws', 'step_seeded'):
+        dt = out[k]['median_ms'] * 1e-3
+        print(f'TSC-diffusion train step ({k}), batch {B} x 2 s: median {dt * 1e3:.1f} ms/step (p90 {out[k]["p90_ms"]:.1f}) = '
+              f'{B / dt:.1f} utt/s')
+    print(f'seeded step within the unseeded step\'s p90 - median ({out["allowed_excess_ms"]:.2f} ms): {out["seeded_within_spread"]}; '
+          f'loss {out["loss"]:.4f}')
+    os.makedirs(os.path.join(ROOT, 'profiles'), exist_ok=True)
+    with open(os.path.join(ROOT, 'profiles', 'tsc_train.json'), 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    if not out['seeded_within_spread']:
+        sys.exit('the seeded step is slower than the unseeded step by more than its spread')
+
+
+if __name__ == '__main__':
+    main()
