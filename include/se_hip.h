@@ -669,6 +669,25 @@ int se_diffuse_noise(const float* clean, const float* noisy, const float* c, con
                      const float* noise, unsigned long long seed, unsigned c2, unsigned c3, int B, long long L, int steps,
                      float* noisy_n, float* x_t, float* combine, void* stream);
 
+/* ---- long recordings: chunks for the batched eval forward, crossfaded back (speech-enhancement_amd/inference.py, LongEnhancer) ----
+ * se_chunk_gather: x [L] fp32, starts [K] int64 (device, samples) -> chunks [K][S] (16-byte aligned, S % 4 == 0, L >= S), c [K],
+ * silent [K] (uint8).  With P_k = sum over the chunk of x^2 in fp64 (thread t of 256 takes the quads t, t + 256, ..., then wave
+ * shuffles, then the four waves in index order):
+ *   chunks[k][i] = x[starts[k] + i] bit for bit,   c[k] = (float)sqrt(S / P_k),   silent[k] = 0
+ *   P_k == 0:  c[k] = 1, silent[k] = 1
+ * starts[k] is arbitrary (no alignment); a chunk that does not lie inside [0, L) is written as zeros (and so comes out silent).
+ * One workgroup per chunk, one launch.
+ * se_chunk_assemble: y [K][S] (the enhanced chunks, still scaled by c), starts ascending -> out [L].  For sample n let k be the
+ * largest index with starts[k] <= n, i = n - starts[k], z_k[i] = silent[k] ? 0 : y[k][i] / c[k] (a select: a silent row is not used):
+ *   k > 0 and i < V:  out[n] = w z_k[i] + (1 - w) z_{k-1}[n - starts[k-1]],   w = (i + 0.5) / V     (fp32)
+ *   otherwise:        out[n] = z_k[i]
+ * A sample that no chunk covers (starts[0] > n, or i >= S) is 0; where chunk k - 1 does not reach n there is no fade.  Every
+ * sample has one writer: no atomics.  Indices are 64-bit (K * S may exceed 2^31). */
+int se_chunk_gather(const float* x, long long L, const long long* starts, int K, int S, float* chunks, float* c,
+                    unsigned char* silent, void* stream);
+int se_chunk_assemble(const float* y, const float* c, const unsigned char* silent, const long long* starts, int K, int S, int V,
+                      float* out, long long L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,3 +21,4 @@ from .data import NoiseBank, BankMix, bank_rng, draw_bank, mix_bank_at_snr  # no
 from .sampler import GraphedTSCSampler, sampler_update, philox_normal  # noqa: F401
 from .tsc_diffusion import noise_coefficients, draw_steps, diffusion_noise, pack_counter  # noqa: F401
 from .train_diffuse import train_tsc_diffusion, validate_tsc_diffusion  # noqa: F401
+from .inference import LongEnhancer, chunk_plan  # noqa: F401

@@ -110,3 +110,104 @@ class GraphedEnhancer:
 
     def __call__(self, noisy_signal):
         return self.enhance_device(noisy_signal).cpu().numpy()
+
+
+def check_chunking(chunk, overlap, hop=100):
+    """the chunk length S and the crossfade length V (samples) a chunk plan accepts"""
+    S, V, hop = int(chunk), int(overlap), int(hop)
+    if hop < 1 or S % hop != 0 or S <= 2 * hop:
+        raise ValueError(f'chunk length {S} must be a multiple of the hop ({hop}) and longer than two hops: the STFT reflect-pads by 2 hops')
+    if V < 1 or 3 * V > S:
+        raise ValueError(f'chunk overlap {V} must lie in [1, chunk / 3 = {S // 3}]: a fade-in has to end before the next chunk starts')
+    return S, V
+
+
+def chunk_plan(length, chunk, overlap, hop=100):
+    """start samples of the chunks of a recording of `length` samples: K chunks of `chunk` = S samples, all of them full of real audio
+    (nothing is padded), the first at 0, the last ending at `length`, spread evenly, neighbours overlapping by at least `overlap` = V:
+        K = max(2, ceil((L - V) / (S - V))),   s_k = (k (L - S)) // (K - 1)
+    so every stride is <= S - V, and for K >= 3 it is >= V (needs 3 V <= S): the fade-in of a chunk over its first V samples is over
+    before the next chunk starts, and every sample belongs to at most two chunks.  length <= S gives [0]: one whole-utterance forward."""
+    S, V = check_chunking(chunk, overlap, hop)
+    L = int(length)
+    if L < 1:
+        raise ValueError(f'chunk_plan: empty recording (length {L})')
+    if L <= S:
+        return [0]
+    K = max(2, -(-(L - V) // (S - V)))
+    return [(k * (L - S)) // (K - 1) for k in range(K)]
+
+
+class LongEnhancer:
+    """Enhances recordings of any length: the recording is cut into overlapping chunks (chunk_plan), each chunk is normalised by its
+    own c = sqrt(S / sum x^2) -- the statistics of the crops the generator was trained on, not of the whole recording --, the chunks
+    run through the generator `batch` at a time (the batched eval forward validate_gan uses), and the enhanced chunks are
+    de-normalised and joined with a linear crossfade over the first `overlap_seconds` of every chunk.  The weights of the fade are
+    amplitude-complementary (they sum to one): both sides estimate the same signal.  Chunks of exact zeros are not forwarded and
+    come out as exact zeros.  A recording no longer than one chunk takes predict()'s whole-utterance arithmetic.
+
+    Everything runs eagerly on the current stream: one copy of the recording to the device, one gather launch (ops.chunk_gather),
+    one copy of the K silence flags back (the only synchronisation), ceil(non-silent K / batch) forwards, one assemble launch
+    (ops.chunk_assemble).  Memory is that of one forward of `batch` chunks plus the recording, its chunks [K, S] twice (in and out) and the result.  Same contract as
+    GraphedEnhancer: enhance_device -> device tensor [L], __call__ -> numpy, so metrics.evaluate(..., enhancer=...) takes it."""
+
+    def __init__(self, model, config, chunk_seconds=4.0, overlap_seconds=0.5, batch=8, device=torch.device('cuda')):
+        rate = getattr(config, 'SAMPLE_RATE', 16000)
+        self.S, self.V = check_chunking(round(chunk_seconds * rate), round(overlap_seconds * rate), config.HOP_SAMPLES)
+        if int(batch) < 1:
+            raise ValueError(f'LongEnhancer: batch must be at least 1, got {batch}')
+        self._require_eval(model)
+        self.model, self.config, self.batch, self.device = model, config, int(batch), device
+        self.forwards = 0               # generator forwards issued so far
+
+    @staticmethod
+    def _require_eval(model):
+        if model.training:
+            raise RuntimeError('LongEnhancer needs model.eval(): BatchNorm must use its running statistics')
+
+    def _whole(self, x):
+        """predict() on a device signal [L], result left on the device"""
+        hop, n_fft = self.config.HOP_SAMPLES, self.config.N_FFT
+        noisy = x.unsqueeze(0)
+        c = O.clip_scale(noisy.contiguous())
+        length = noisy.size(-1)
+        padding_len = int(np.ceil(length / hop)) * hop - length
+        noisy = torch.cat([noisy, noisy[:, :padding_len]], dim=-1)
+        planes, _ = FE.stft_planes(noisy, n_fft, hop, 'pow', scale=c, padded=False)
+        self.forwards += 1
+        est = self.model.forward_planes(planes)
+        est_audio = FE.istft_planes(est, n_fft, hop, 'pow') / c[:, None]
+        return torch.flatten(est_audio)[:length]
+
+    @torch.no_grad()
+    def enhance_chunks(self, x):
+        """x: device signal [L], L > S -> (y [K, S], c [K], silent [K], starts [K]): the enhanced chunks still scaled by c (rows of
+        silent chunks are zeros), as ops.chunk_assemble takes them"""
+        self._require_eval(self.model)
+        hop, n_fft = self.config.HOP_SAMPLES, self.config.N_FFT
+        plan = chunk_plan(x.numel(), self.S, self.V, hop)
+        starts = torch.tensor(plan, dtype=torch.int64).to(x.device)
+        chunks, c, silent = O.chunk_gather(x, starts, self.S)
+        live = torch.nonzero(silent.cpu() == 0).flatten()
+        y = torch.zeros_like(chunks)
+        live_dev = live.to(x.device)
+        for g in range(0, live.numel(), self.batch):
+            rows = live_dev[g:g + self.batch]
+            planes, _ = FE.stft_planes(chunks.index_select(0, rows), n_fft, hop, 'pow', scale=c.index_select(0, rows), padded=False)
+            self.forwards += 1
+            est = self.model.forward_planes(planes)
+            y.index_copy_(0, rows, FE.istft_planes(est, n_fft, hop, 'pow'))
+        return y, c, silent, starts
+
+    @torch.no_grad()
+    def enhance_device(self, noisy_signal):
+        """the enhanced recording as a device tensor [length], complete on the current stream"""
+        self._require_eval(self.model)
+        x = torch.as_tensor(np.asarray(noisy_signal, dtype=np.float32).reshape(-1)).to(self.device)
+        if x.numel() <= self.S:
+            return self._whole(x)
+        y, c, silent, starts = self.enhance_chunks(x)
+        return O.chunk_assemble(y, c, silent, starts, self.V, x.numel())
+
+    def __call__(self, noisy_signal):
+        return self.enhance_device(noisy_signal).cpu().numpy()

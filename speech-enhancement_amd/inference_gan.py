@@ -1,7 +1,10 @@
 """inference_gan.py command line (flags :29-52, loop :102-162).  Enhances every wav under config.DATA.TEST_NOISY_DIR, scores it
 against the file of the same name under config.DATA.TEST_CLEAN_DIR on the device (metrics.evaluate) and prints the reference's
 line `pesq csig cbak covl ssnr stoi`; `--validate-epochs` does so for checkpoint_{start..end-1} and names the best epoch.
-Without clean files it only enhances (and saves with --save).  Needs a wav reader (scipy.io.wavfile)."""
+Without clean files it only enhances (and saves with --save).  Needs a wav reader (scipy.io.wavfile).
+--chunk-len SEC > 0 enhances every recording in overlapping chunks of SEC seconds, --chunk-batch of them per forward, crossfaded over
+--chunk-overlap seconds (inference.LongEnhancer): for recordings too long for one whole-utterance forward.  The default 0 is the
+reference's whole-utterance forward."""
 import argparse
 import glob
 import os
@@ -11,7 +14,7 @@ import torch
 
 from . import metrics
 from .config import get_config
-from .inference import load_model, predict
+from .inference import LongEnhancer, check_chunking, load_model, predict
 
 
 def parse_option(argv=None):
@@ -25,8 +28,25 @@ def parse_option(argv=None):
     p.add_argument('--end', default=None, type=int)
     p.add_argument('--gpu', default=0, type=int)
     p.add_argument('--opts', default=None, nargs='+')
+    p.add_argument('--chunk-len', default=0.0, type=float, metavar='SEC')
+    p.add_argument('--chunk-overlap', default=0.5, type=float, metavar='SEC')
+    p.add_argument('--chunk-batch', default=8, type=int, metavar='N')
     args, _ = p.parse_known_args(argv)
-    return args, get_config(args)
+    config = get_config(args)
+    if args.chunk_len < 0:
+        raise ValueError(f'--chunk-len must be 0 (whole utterances) or a chunk length in seconds, got {args.chunk_len}')
+    if args.chunk_len > 0:
+        check_chunking(round(args.chunk_len * config.SAMPLE_RATE), round(args.chunk_overlap * config.SAMPLE_RATE), config.HOP_SAMPLES)
+        if args.chunk_batch < 1:
+            raise ValueError(f'--chunk-batch must be at least 1, got {args.chunk_batch}')
+    return args, config
+
+
+def long_enhancer(args, config, model, device):
+    """the chunked enhancer the --chunk-* flags ask for, or None for the whole-utterance default"""
+    if args.chunk_len <= 0:
+        return None
+    return LongEnhancer(model, config, args.chunk_len, args.chunk_overlap, args.chunk_batch, device)
 
 
 def _read(path, config):
@@ -56,7 +76,7 @@ def inference(args, config, model_path, data_paths, device):
     noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
     pairs = ((_read(p, config), _read(p.replace(noisy_dir, clean_dir), config)) for p in data_paths)
     save = (lambda i, est: _save(args, config, data_paths[i], est.cpu().numpy())) if args.save else None
-    return metrics.evaluate(model, config, pairs, on_enhanced=save)
+    return metrics.evaluate(model, config, pairs, on_enhanced=save, enhancer=long_enhancer(args, config, model, device))
 
 
 def main(argv=None):
@@ -69,8 +89,10 @@ def main(argv=None):
     if not all(os.path.exists(p.replace(noisy_dir, clean_dir)) for p in data_paths) or not os.path.isdir(clean_dir):
         print(f'no clean signals under DATA.TEST_CLEAN_DIR ({clean_dir}): enhancing only, no metrics')
         model = load_model(args.model_path, config, device)
+        chunked = long_enhancer(args, config, model, device)
         for path in data_paths:
-            y = predict(model, config, _read(path, config), device)
+            x = _read(path, config)
+            y = chunked(x) if chunked is not None else predict(model, config, x, device)
             if args.save:
                 _save(args, config, path, y)
         return

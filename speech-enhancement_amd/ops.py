@@ -400,3 +400,37 @@ def axpbypcz(a, b, c, alpha, beta, gamma, out=None):
     L.call('se_axpbypcz', L.ptr(a), L.ptr(b), L.ptr(c), L.ptr(out), _f(alpha), _f(beta), _f(gamma), _l(a.numel()),
            L.stream())
     return out
+
+
+def _chunk_args(starts, *fp32):
+    L.check_cuda(starts, *fp32)
+    if starts.dtype != torch.int64 or starts.dim() != 1 or not starts.is_contiguous():
+        raise L.SeHipError('chunk starts must be a contiguous int64 vector')
+    for t in fp32:
+        if t.dtype != f32 or not t.is_contiguous():
+            raise L.SeHipError('chunk operands must be contiguous fp32 tensors')
+
+
+def chunk_gather(x, starts, S):
+    """x [L], starts [K] int64 (device) -> (chunks [K, S], c [K], silent [K] uint8): chunks[k] = x[starts[k] : starts[k] + S],
+    c[k] = sqrt(S / sum chunk^2) in fp64, a chunk of exact zeros has c = 1 and silent = 1 (se_chunk_gather, include/se_hip.h)"""
+    _chunk_args(starts, x)
+    K = starts.numel()
+    if x.dim() != 1 or K < 1 or S % 4 != 0 or x.numel() < S:
+        raise L.SeHipError(f'chunk_gather: need a signal [L] with L >= S, S % 4 == 0 and K >= 1 (L={x.numel()}, S={S}, K={K})')
+    chunks, c = _new(K, S, like=x), _new(K, like=x)
+    silent = _new(K, like=x, dtype=torch.uint8)
+    L.call('se_chunk_gather', L.ptr(x), x.numel(), L.ptr(starts), K, S, L.ptr(chunks), L.ptr(c), L.ptr(silent), L.stream())
+    return chunks, c, silent
+
+
+def chunk_assemble(y, c, silent, starts, V, length):
+    """the enhanced chunks y [K, S] (scaled by c [K]) -> out [length]: each chunk de-normalised, the first V samples of a chunk
+    crossfaded linearly with the chunk before it, silent chunks exact zeros (se_chunk_assemble, include/se_hip.h)"""
+    _chunk_args(starts, y, c)
+    K, S = y.shape
+    if starts.numel() != K or c.numel() != K or silent.numel() != K or silent.dtype != torch.uint8 or not silent.is_cuda:
+        raise L.SeHipError('chunk_assemble: c, silent (uint8) and starts must have one entry per row of y')
+    out = _new(int(length), like=y)
+    L.call('se_chunk_assemble', L.ptr(y), L.ptr(c), L.ptr(silent), L.ptr(starts), K, S, int(V), L.ptr(out), int(length), L.stream())
+    return out
