@@ -34,10 +34,16 @@ def dft_matrices(n_fft, hop, device):
         return _CACHE[key]
     Fq = n_fft // 2 + 1
     w = hamming(n_fft, device)
-    k = torch.arange(n_fft, dtype=torch.float64, device=device)
-    f = torch.arange(Fq, dtype=torch.float64, device=device)
-    ang = 2.0 * math.pi * f[:, None] * k[None, :] / n_fft             # [F, n_fft]
-    Wf = torch.cat([torch.cos(ang) * w, -torch.sin(ang) * w], 0)        # rows: re_f | im_f
+    k = torch.arange(n_fft, dtype=torch.int64, device=device)
+    f = torch.arange(Fq, dtype=torch.int64, device=device)
+    # f k mod n in integers: the angle stays in [0, 2 pi), and the entries that are exactly zero are zero.  Taken at 2 pi f k / n
+    # (up to 1250 rad) they were rounding noise of 1e-13, which is all there is in the Im column of the Nyquist bin
+    m = (f[:, None] * k[None, :]) % n_fft                               # [F, n_fft]
+    ang = 2.0 * math.pi * m.double() / n_fft
+    zero = torch.zeros_like(ang)
+    cos = torch.where((4 * m) % (2 * n_fft) == n_fft, zero, torch.cos(ang))
+    sin = torch.where((2 * m) % n_fft == 0, zero, torch.sin(ang))
+    Wf = torch.cat([cos * w, -sin * w], 0)                              # rows: re_f | im_f
     # inverse: frame[k] = w[k]/n * sum_f c_f (re_f cos - im_f sin), c_0 = c_{n/2} = 1 else 2
     c = torch.full((Fq,), 2.0, dtype=torch.float64, device=device)
     c[0] = 1.0
@@ -45,8 +51,8 @@ def dft_matrices(n_fft, hop, device):
         c[-1] = 1.0
     Kp = _ceil4(2 * Fq)
     Wi = torch.zeros(n_fft, Kp, dtype=torch.float64, device=device)
-    Wi[:, :Fq] = (torch.cos(ang) * c[:, None]).T * w[:, None] / n_fft
-    Wi[:, Fq:2 * Fq] = (-torch.sin(ang) * c[:, None]).T * w[:, None] / n_fft
+    Wi[:, :Fq] = (cos * c[:, None]).T * w[:, None] / n_fft
+    Wi[:, Fq:2 * Fq] = (-sin * c[:, None]).T * w[:, None] / n_fft
     out = (Wf.float().contiguous(), Wi.float().contiguous(), w)
     _CACHE[key] = out
     return out
