@@ -688,6 +688,33 @@ int se_chunk_gather(const float* x, long long L, const long long* starts, int K,
 int se_chunk_assemble(const float* y, const float* c, const unsigned char* silent, const long long* starts, int K, int S, int V,
                       float* out, long long L, void* stream);
 
+/* ---- streaming: B live streams, fixed window, state on the device (speech-enhancement_amd/inference.py, StreamEnhancer) ----
+ * Sizes in samples: W window (the model's context), H block (pushed per step), A look-ahead withheld at the window's right edge,
+ * V crossfade, D = A + V the delay.  H % 4 == 0, W % 4 == 0, 1 <= V <= H, A >= 0, H + D <= W; H need not divide W.
+ * State of row b: the samples x_b[0 .. n_b) received so far, n_b = pos[b] (int64, a multiple of H); the last W of them in
+ * ring [B][W], sample g at slot g mod W; tail [B][D].  A step of a row is taken with n = pos[b] + H, the count after the block.
+ * se_stream_window: block [B][H] -> ring (the block's H slots), window [B][W], c [B], silent [B] (uint8); block, ring, window
+ * 16-byte aligned.  pos is read, NOT advanced (se_stream_emit does that, so both kernels of a step see the same counter):
+ *   ring[b][(pos[b] + j) mod W] = block[b][j]                                  (the slots of the H oldest samples)
+ *   window[b][i] = x_b[n - W + i] bit for bit, 0 where n - W + i < 0           (i in [0, W))
+ *   P = sum window^2 in fp64 (thread t of 256 takes the quads t, t + 256, ..., then wave shuffles, then the four waves in index
+ *   order), r = min(n, W):   c[b] = (float)sqrt(r / P), silent[b] = 0;   P == 0:  c[b] = 1, silent[b] = 1
+ * The window reads ring slots the block does not write: no read-after-write inside the launch.  A block wraps around the ring's
+ * end whenever pos mod W + H > W.  A row with pos[b] < 0 (no state this library produces) gets a zero window and keeps its ring.
+ * One workgroup per row, one launch.
+ * se_stream_emit: y [B][W] (the enhanced windows, still scaled by c) -> out [B][H], tail, pos.  e[i] = silent[b] ? 0 : y[b][i] / c[b]
+ * (a select: a silent row of y is not used, whatever it holds).  out[b][j] carries global sample g = n - H - D + j:
+ *   v = e[W - H - D + j];   j < V:  w = (j + 0.5) / V,  v = w v + (1 - w) tail[b][j]      (fp32, the ramp of se_chunk_assemble)
+ *   out[b][j] = g < 0 ? 0 : v
+ * then tail[b][j] = e[W - D + j] for j in [0, D) and pos[b] += H.  tail[b][j] is read (j < V) by the lane that then overwrites
+ * it; every element of out and tail has one writer: no atomics.  One workgroup per row, one launch.
+ * Flushing a stream is reading its tail (global samples [n - D, n) of the last estimate); resetting a row is zeroing its counter,
+ * its ring row and its tail row: neither needs a kernel of its own. */
+int se_stream_window(const float* block, float* ring, const long long* pos, int B, int H, int W, float* window, float* c,
+                     unsigned char* silent, void* stream);
+int se_stream_emit(const float* y, const float* c, const unsigned char* silent, float* tail, long long* pos, int B, int H, int W,
+                   int A, int V, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,9 @@ def lib():
                                ('se_crop_gather_bank', [p, p, q, p, q, p, p, i, i, p, p, p, p, p, C.c_size_t, p]),
                                ('se_crop_gather_mix_workspace_bytes', [i, i]),
                                ('se_chunk_gather', [p, q, p, i, i, p, p, p, p]),
-                               ('se_chunk_assemble', [p, p, p, p, i, i, i, p, q, p])):
+                               ('se_chunk_assemble', [p, p, p, p, i, i, i, p, q, p]),
+                               ('se_stream_window', [p, p, p, i, i, i, p, p, p, p]),
+                               ('se_stream_emit', [p, p, p, p, p, i, i, i, i, i, p, p])):
             if hasattr(_lib, name):
                 getattr(_lib, name).argtypes = argtypes
         if hasattr(_lib, 'se_crop_gather_mix_workspace_bytes'):

@@ -22,3 +22,4 @@ from .sampler import GraphedTSCSampler, sampler_update, philox_normal  # noqa: F
 from .tsc_diffusion import noise_coefficients, draw_steps, diffusion_noise, pack_counter  # noqa: F401
 from .train_diffuse import train_tsc_diffusion, validate_tsc_diffusion  # noqa: F401
 from .inference import LongEnhancer, chunk_plan  # noqa: F401
+from .inference import StreamEnhancer, check_streaming  # noqa: F401

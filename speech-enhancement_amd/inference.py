@@ -211,3 +211,165 @@ class LongEnhancer:
 
     def __call__(self, noisy_signal):
         return self.enhance_device(noisy_signal).cpu().numpy()
+
+
+def check_streaming(window, block, lookahead, fade, hop=100):
+    """the window W, block H, look-ahead A and crossfade V (samples) a stream accepts -> (W, H, A, V); the delay is D = A + V"""
+    W, H, A, V, hop = int(window), int(block), int(lookahead), int(fade), int(hop)
+    if hop < 1 or W % hop != 0 or W <= 2 * hop or W % 4 != 0:
+        raise ValueError(f'stream window {W} must be a multiple of the hop ({hop}) and of 4 and longer than two hops: the STFT reflect-pads by 2 hops')
+    if H < 4 or H % 4 != 0:
+        raise ValueError(f'stream block {H} must be a positive multiple of 4 samples')
+    if V < 1 or V > H:
+        raise ValueError(f'stream fade {V} must lie in [1, block = {H}]: a fade has to end inside the block it starts in')
+    if A < 0:
+        raise ValueError(f'stream lookahead {A} must not be negative')
+    if H + A + V > W:
+        raise ValueError(f'stream block + lookahead + fade = {H + A + V} must fit into the window ({W})')
+    return W, H, A, V
+
+
+def stream_plan(length, block, delay):
+    """offline use of a stream on a recording of `length` samples: (K, lo, hi) -- push K = ceil(length / H) blocks (the last one
+    zero-padded), append the flush, and samples [lo, hi) = [D, D + length) of that concatenation (K H + D samples) are the
+    enhanced recording, aligned with the input"""
+    L, H, D = int(length), int(block), int(delay)
+    if L < 1:
+        raise ValueError(f'stream_plan: empty recording (length {L})')
+    return -(-L // H), D, D + L
+
+
+class StreamEnhancer:
+    """Enhances `streams` = B live streams side by side, a block of H samples per stream and step, with a bounded delay.  Per row
+    the device keeps a ring of the last W input samples, an int64 sample counter and the withheld tail of the previous estimate
+    (include/se_hip.h, "streaming").  A step pushes one block per row:
+      1. ops.stream_window: the block enters the ring; the window is the last W samples (zeros on the left until W have arrived),
+         normalised by its own c = sqrt(r / sum x^2) over its r = min(n, W) real samples -- the statistic of the training crops;
+      2. the batched eval forward LongEnhancer uses: STFT -> generator -> iSTFT of c * window;
+      3. ops.stream_emit: the H samples that lie D = A + V behind the window's right edge come out, the first V of them crossfaded
+         (linear, weights summing to one) with the tail the previous step withheld; the last D samples become the new tail.
+    So every emitted sample was estimated with at least A samples of look-ahead (those of the crossfade with at least A + 1),
+    the algorithmic latency is H + A + V samples (`latency_seconds`) plus the time of one step, and the pushed outputs followed by
+    flush(), with the first D samples dropped, are the enhanced samples aligned with the input.  Nothing but the input ring and the
+    tail passes from step to step -- nothing goes through the model twice --, so a step cannot poison the next.  A row whose window
+    is exact zeros is still forwarded (the step has one shape, and a graph cannot branch) and comes out as exact zeros through a
+    select; rows do not interact beyond the rounding of the forward's shared operand scales (eval mode: InstanceNorm is per
+    sample, BatchNorm uses its running statistics).  All rows step together; a row without audio in a step is pushed zeros.
+
+    graph=True captures the whole step into ONE HIP graph over static [B, H] input and output buffers (warm-up on a side stream
+    and capture as GraphedEnhancer does; the state is reset after the warm-up): push() is one copy plus one replay.  graph=False
+    issues the same launches eagerly.  Neither path synchronises with the host.  The tensor push() returns is the static output
+    buffer: valid until the next push.  Same contract as LongEnhancer for whole recordings: enhance_device -> device tensor [L]
+    (streams == 1), __call__ -> numpy, so metrics.evaluate(..., enhancer=...) takes it; the last partial block is zero-padded, so
+    the final windows of such an offline run see zeros in their look-ahead."""
+
+    def __init__(self, model, config, window_seconds=2.0, block_seconds=0.1, lookahead_seconds=0.05, fade_seconds=0.01, streams=1,
+                 device=torch.device('cuda'), graph=True):
+        rate = getattr(config, 'SAMPLE_RATE', 16000)
+        self.W, self.H, self.A, self.V = check_streaming(round(window_seconds * rate), round(block_seconds * rate),
+                                                         round(lookahead_seconds * rate), round(fade_seconds * rate), config.HOP_SAMPLES)
+        if int(streams) < 1:
+            raise ValueError(f'StreamEnhancer: streams must be at least 1, got {streams}')
+        LongEnhancer._require_eval(model)
+        self.model, self.config, self.B, self.device, self.rate = model, config, int(streams), device, rate
+        self.delay = self.A + self.V
+        self.latency_seconds = (self.H + self.delay) / rate
+        self.steps = 0                  # steps issued so far
+        self._graph = None
+        B, kw = self.B, {'device': device, 'dtype': torch.float32}
+        self.ring, self.tail = torch.zeros(B, self.W, **kw), torch.zeros(B, self.delay, **kw)
+        self.pos = torch.zeros(B, device=device, dtype=torch.int64)
+        self._in, self._out = torch.zeros(B, self.H, **kw), torch.zeros(B, self.H, **kw)
+        self._window, self._c = torch.zeros(B, self.W, **kw), torch.ones(B, **kw)
+        self._silent = torch.zeros(B, device=device, dtype=torch.uint8)
+        if graph:
+            self._capture()
+
+    def _step(self):
+        cfg = self.config
+        O.stream_window(self._in, self.ring, self.pos, self._window, self._c, self._silent)
+        planes, _ = FE.stft_planes(self._window, cfg.N_FFT, cfg.HOP_SAMPLES, 'pow', scale=self._c, padded=False)
+        est = self.model.forward_planes(planes)
+        y = FE.istft_planes(est, cfg.N_FFT, cfg.HOP_SAMPLES, 'pow')
+        O.stream_emit(y, self._c, self._silent, self.tail, self.pos, self.H, self.A, self.V, self._out)
+
+    def _capture(self):
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._in.normal_(0.0, 0.1)                # warm-up on non-degenerate data
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    self._step()
+            torch.cuda.current_stream().wait_stream(side)
+            self.reset()                              # the warm-up advanced the state
+            self._in.zero_()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._step()
+        torch.cuda.synchronize()
+        self._graph = g
+
+    def reset(self, rows=None):
+        """forget everything the named rows (default: all) have received: counter, ring row and tail row are zeroed"""
+        if rows is None:
+            for t in (self.ring, self.tail, self.pos):
+                t.zero_()
+            return
+        rows = [int(r) for r in np.atleast_1d(rows)]
+        if any(r < 0 or r >= self.B for r in rows):
+            raise ValueError(f'StreamEnhancer.reset: rows {rows} outside [0, {self.B})')
+        idx = torch.tensor(rows, dtype=torch.int64).to(self.device, non_blocking=True)
+        for t in (self.ring, self.tail, self.pos):
+            t.index_fill_(0, idx, 0)
+
+    @torch.no_grad()
+    def push(self, blocks):
+        """blocks [B, H] (device tensor or array; [H] with one stream) -> the device tensor [B, H] of enhanced samples that lie D
+        behind them, complete on the current stream and valid until the next push"""
+        LongEnhancer._require_eval(self.model)
+        if not torch.is_tensor(blocks):
+            blocks = torch.from_numpy(np.ascontiguousarray(blocks, dtype=np.float32))
+        if blocks.numel() != self.B * self.H or blocks.dim() > 2:
+            raise ValueError(f'StreamEnhancer.push: need blocks [{self.B}, {self.H}], got {tuple(blocks.shape)}')
+        self._in.copy_(blocks.reshape(self.B, self.H), non_blocking=True)
+        if self._graph is not None:
+            self._graph.replay()
+        else:
+            self._step()
+        self.steps += 1
+        return self._out
+
+    def flush(self):
+        """the withheld tail [B, D]: global samples [n - D, n) of the last estimate.  No forward; the state is left as it is."""
+        return self.tail.clone()
+
+    @torch.no_grad()
+    def enhance_batch(self, signals):
+        """up to `streams` recordings of any lengths, one per row -> list of device tensors, each of its recording's own length.
+        All rows are reset first; a row whose recording has ended is pushed zeros."""
+        sigs = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
+        if not 1 <= len(sigs) <= self.B:
+            raise ValueError(f'StreamEnhancer.enhance_batch: need 1 to {self.B} signals, got {len(sigs)}')
+        plans = [stream_plan(s.shape[0], self.H, self.delay) for s in sigs]
+        K, H = max(p[0] for p in plans), self.H
+        host = np.zeros((self.B, K * H), np.float32)
+        for b, s in enumerate(sigs):
+            host[b, :s.shape[0]] = s
+        x = torch.from_numpy(host).to(self.device)
+        res = torch.empty(self.B, K * H + self.delay, device=self.device, dtype=torch.float32)
+        self.reset()
+        for k in range(K):
+            res[:, k * H:(k + 1) * H] = self.push(x[:, k * H:(k + 1) * H])
+        res[:, K * H:] = self.tail
+        return [res[b, lo:hi] for b, (_, lo, hi) in enumerate(plans)]
+
+    def enhance_device(self, noisy_signal):
+        """the recording streamed through row 0 block by block, as if it had arrived live -> device tensor [length]"""
+        if self.B != 1:
+            raise ValueError(f'StreamEnhancer.enhance_device runs one recording on one stream; this one has {self.B} (use enhance_batch)')
+        return self.enhance_batch([noisy_signal])[0]
+
+    def __call__(self, noisy_signal):
+        return self.enhance_device(noisy_signal).cpu().numpy()

@@ -4,7 +4,10 @@ line `pesq csig cbak covl ssnr stoi`; `--validate-epochs` does so for checkpoint
 Without clean files it only enhances (and saves with --save).  Needs a wav reader (scipy.io.wavfile).
 --chunk-len SEC > 0 enhances every recording in overlapping chunks of SEC seconds, --chunk-batch of them per forward, crossfaded over
 --chunk-overlap seconds (inference.LongEnhancer): for recordings too long for one whole-utterance forward.  The default 0 is the
-reference's whole-utterance forward."""
+reference's whole-utterance forward.
+--stream-block SEC > 0 enhances every recording as if it had arrived live, SEC seconds at a time, through a window of --stream-window
+seconds with --stream-lookahead seconds withheld and a crossfade of --stream-fade seconds (inference.StreamEnhancer): the metrics
+then show what streaming costs with the checkpoint at hand.  Not together with --chunk-len."""
 import argparse
 import glob
 import os
@@ -14,7 +17,7 @@ import torch
 
 from . import metrics
 from .config import get_config
-from .inference import LongEnhancer, check_chunking, load_model, predict
+from .inference import LongEnhancer, StreamEnhancer, check_chunking, check_streaming, load_model, predict
 
 
 def parse_option(argv=None):
@@ -31,6 +34,7 @@ def parse_option(argv=None):
     p.add_argument('--chunk-len', default=0.0, type=float, metavar='SEC')
     p.add_argument('--chunk-overlap', default=0.5, type=float, metavar='SEC')
     p.add_argument('--chunk-batch', default=8, type=int, metavar='N')
+    add_stream_flags(p)
     args, _ = p.parse_known_args(argv)
     config = get_config(args)
     if args.chunk_len < 0:
@@ -39,14 +43,41 @@ def parse_option(argv=None):
         check_chunking(round(args.chunk_len * config.SAMPLE_RATE), round(args.chunk_overlap * config.SAMPLE_RATE), config.HOP_SAMPLES)
         if args.chunk_batch < 1:
             raise ValueError(f'--chunk-batch must be at least 1, got {args.chunk_batch}')
+    check_stream_flags(args, config)
     return args, config
 
 
+def add_stream_flags(p):
+    p.add_argument('--stream-block', default=0.0, type=float, metavar='SEC')
+    p.add_argument('--stream-window', default=2.0, type=float, metavar='SEC')
+    p.add_argument('--stream-lookahead', default=0.05, type=float, metavar='SEC')
+    p.add_argument('--stream-fade', default=0.01, type=float, metavar='SEC')
+
+
+def check_stream_flags(args, config):
+    """refuses what StreamEnhancer would refuse, without touching the GPU; --stream-block 0 = off, the other flags are not looked at"""
+    if args.stream_block < 0:
+        raise ValueError(f'--stream-block must be 0 (off) or a block length in seconds, got {args.stream_block}')
+    if args.stream_block > 0:
+        if getattr(args, 'chunk_len', 0) > 0:
+            raise ValueError('--stream-block and --chunk-len exclude each other: a recording is streamed or chunked, not both')
+        rate = config.SAMPLE_RATE
+        check_streaming(round(args.stream_window * rate), round(args.stream_block * rate), round(args.stream_lookahead * rate),
+                        round(args.stream_fade * rate), config.HOP_SAMPLES)
+
+
 def long_enhancer(args, config, model, device):
-    """the chunked enhancer the --chunk-* flags ask for, or None for the whole-utterance default"""
+    """the chunked enhancer the --chunk-* flags ask for, the streaming one the --stream-* flags ask for, or None for the
+    whole-utterance default"""
+    if getattr(args, 'stream_block', 0) > 0:
+        return stream_enhancer(args, config, model, device)
     if args.chunk_len <= 0:
         return None
     return LongEnhancer(model, config, args.chunk_len, args.chunk_overlap, args.chunk_batch, device)
+
+
+def stream_enhancer(args, config, model, device):
+    return StreamEnhancer(model, config, args.stream_window, args.stream_block, args.stream_lookahead, args.stream_fade, 1, device)
 
 
 def _read(path, config):

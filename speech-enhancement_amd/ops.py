@@ -434,3 +434,51 @@ def chunk_assemble(y, c, silent, starts, V, length):
     out = _new(int(length), like=y)
     L.call('se_chunk_assemble', L.ptr(y), L.ptr(c), L.ptr(silent), L.ptr(starts), K, S, int(V), L.ptr(out), int(length), L.stream())
     return out
+
+
+def _stream_args(pos, B, *fp32, silent=None):
+    L.check_cuda(pos, silent, *fp32)
+    if pos.dtype != torch.int64 or pos.dim() != 1 or pos.numel() != B or not pos.is_contiguous():
+        raise L.SeHipError('stream pos must be a contiguous int64 vector with one entry per row')
+    for t in fp32:
+        if t.dtype != f32 or not t.is_contiguous() or t.shape[0] != B:
+            raise L.SeHipError('stream operands must be contiguous fp32 tensors with one row per stream')
+    if silent is not None and (silent.dtype != torch.uint8 or silent.shape != (B,) or not silent.is_contiguous()):
+        raise L.SeHipError('stream silent must be a contiguous uint8 vector with one entry per row')
+
+
+def stream_window(block, ring, pos, window=None, c=None, silent=None):
+    """block [B, H], ring [B, W], pos [B] int64 -> (window [B, W], c [B], silent [B] uint8): the block goes into the ring at slots
+    (pos + j) mod W, the window is the last W samples after the block (zeros where the stream has none yet),
+    c = sqrt(min(pos + H, W) / sum window^2) in fp64, a window of exact zeros has c = 1 and silent = 1.  pos is left as it is
+    (se_stream_window, include/se_hip.h).  window, c, silent: optional outputs to write into (static buffers of a graph)."""
+    if block.dim() != 2 or ring.dim() != 2:
+        raise L.SeHipError('stream_window: need block [B, H] and ring [B, W]')
+    (B, H), W = block.shape, ring.shape[1]
+    window = _new(B, W, like=ring) if window is None else window
+    c = _new(B, like=ring) if c is None else c
+    silent = _new(B, like=ring, dtype=torch.uint8) if silent is None else silent
+    _stream_args(pos, B, block, ring, window, c, silent=silent)
+    if H < 1 or H % 4 != 0 or W % 4 != 0 or H > W or window.shape != (B, W) or c.shape != (B,):
+        raise L.SeHipError(f'stream_window: need H % 4 == 0, W % 4 == 0, H <= W, window [B, W] and c [B] (B={B}, H={H}, W={W})')
+    L.call('se_stream_window', L.ptr(block), L.ptr(ring), L.ptr(pos), B, H, W, L.ptr(window), L.ptr(c), L.ptr(silent), L.stream())
+    return window, c, silent
+
+
+def stream_emit(y, c, silent, tail, pos, H, A, V, out=None):
+    """y [B, W] (the enhanced windows, scaled by c [B]), tail [B, A + V], pos [B] int64 -> out [B, H]: the H samples that lie
+    D = A + V behind the window's right edge, de-normalised, their first V crossfaded with the tail; then the tail is the last D
+    samples of the de-normalised window and pos += H.  Silent rows give exact zeros in both (se_stream_emit, include/se_hip.h)."""
+    H, A, V = int(H), int(A), int(V)
+    if y.dim() != 2 or tail.dim() != 2:
+        raise L.SeHipError('stream_emit: need y [B, W] and tail [B, D]')
+    B, W = y.shape
+    if H < 1 or H % 4 != 0 or V < 1 or V > H or A < 0 or H + A + V > W or tail.shape[1] != A + V:
+        raise L.SeHipError(f'stream_emit: need H % 4 == 0, 1 <= V <= H, A >= 0, H + A + V <= W and tail [B, A + V] '
+                           f'(H={H}, A={A}, V={V}, W={W}, tail {tuple(tail.shape)})')
+    out = _new(B, H, like=y) if out is None else out
+    _stream_args(pos, B, y, c, tail, out, silent=silent)
+    if out.shape != (B, H) or c.shape != (B,):
+        raise L.SeHipError('stream_emit: need out [B, H] and c [B]')
+    L.call('se_stream_emit', L.ptr(y), L.ptr(c), L.ptr(silent), L.ptr(tail), L.ptr(pos), B, H, W, A, V, L.ptr(out), L.stream())
+    return out
