@@ -10,6 +10,15 @@ import torch
 from . import frontend as FE
 from . import ops as O
 from .generator import TSCNet
+from .utils import strip_module_prefix
+
+
+def load_checkpoint_into(model, path, key, device):
+    """checkpoint[key] -> model (the 'module.' prefix of DDP checkpoints stripped where present), eval()"""
+    checkpoint = torch.load(path, map_location=device)
+    model.load_state_dict(strip_module_prefix(checkpoint[key]))
+    model.eval()
+    return model
 
 
 def load_model(model_path, config, device=torch.device('cuda')):
@@ -17,99 +26,138 @@ def load_model(model_path, config, device=torch.device('cuda')):
     7 characters from every key because its checkpoints always come from DDP ('module.' prefix, main_gan.py:142);
     here the prefix is stripped only where present, so single-GPU checkpoints of this package load as well."""
     model = TSCNet(num_channel=64, num_features=config.N_FFT // 2 + 1).to(device)
-    checkpoint = torch.load(model_path, map_location=device)
-    sd = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in checkpoint['gen_state_dict'].items())
-    model.load_state_dict(sd)
-    model.eval()
-    return model
+    return load_checkpoint_into(model, model_path, 'gen_state_dict', device)
+
+
+def hop_frames(length, hop):
+    """(frames, pad): the STFT frames of `length` samples and the samples missing to frames * hop, which the reference fills
+    with the head of the signal (inference_gan.py:84-87)"""
+    frames = int(np.ceil(length / hop))
+    return frames, frames * hop - length
+
+
+def spectral_forward(model, config, x, *cond, scale=None, comp='pow', **kw):
+    """STFT of x [B, L] (times scale [B]) -> model.forward_planes(planes, *cond, **kw) -> iSTFT: device tensor [B, L].  Nothing
+    else: de-normalising, truncating and no_grad are the caller's."""
+    planes, _ = FE.stft_planes(x, config.N_FFT, config.HOP_SAMPLES, comp, scale=scale, padded=False)
+    return FE.istft_planes(model.forward_planes(planes, *cond, **kw), config.N_FFT, config.HOP_SAMPLES, comp)
 
 
 @torch.no_grad()
-def predict(model, config, noisy_signal, device=torch.device('cuda')):
-    """inference_gan.py:75-100: normalise by c, wrap-pad the head of the signal to a multiple of the hop, STFT ->
-    generator -> iSTFT, de-normalise, truncate."""
-    noisy = torch.as_tensor(np.asarray(noisy_signal), dtype=torch.float32, device=device).unsqueeze(0)
-    hop, n_fft = config.HOP_SAMPLES, config.N_FFT
+def predict_device(model, config, x):
+    """inference_gan.py:75-100 on a device signal [L], result left on the device: normalise by c, wrap-pad the head of the
+    signal to a multiple of the hop, STFT -> generator -> iSTFT, de-normalise, truncate."""
+    noisy = x.unsqueeze(0)
     c = O.clip_scale(noisy.contiguous())
     length = noisy.size(-1)
-    frame_num = int(np.ceil(length / hop))
-    padding_len = frame_num * hop - length
+    _, padding_len = hop_frames(length, config.HOP_SAMPLES)
     noisy = torch.cat([noisy, noisy[:, :padding_len]], dim=-1)
-    planes, _ = FE.stft_planes(noisy, n_fft, hop, 'pow', scale=c, padded=False)
-    est = model.forward_planes(planes)
-    est_audio = FE.istft_planes(est, n_fft, hop, 'pow') / c[:, None]
-    est_audio = torch.flatten(est_audio)[:length].cpu().numpy()
-    assert len(est_audio) == length, "Estimated audio and the origin audio must have the same length"
+    est_audio = spectral_forward(model, config, noisy, scale=c) / c[:, None]
+    return torch.flatten(est_audio)[:length]
+
+
+def predict(model, config, noisy_signal, device=torch.device('cuda')):
+    """predict_device on a host signal, result on the host"""
+    noisy = torch.as_tensor(np.asarray(noisy_signal), dtype=torch.float32, device=device)
+    est_audio = predict_device(model, config, noisy).cpu().numpy()
+    assert len(est_audio) == noisy.size(-1), "Estimated audio and the origin audio must have the same length"
     return est_audio
 
 
-class GraphedEnhancer:
-    """predict() with the whole device-side pipeline (STFT, generator, iSTFT, de-normalisation) captured into HIP graphs,
+def capture(step, device, restore=None):
+    """step() captured into a HIP graph on `device` -> (graph, what the captured call of step returned).  All kernels are launched
+    on torch's current stream, which is the capture stream inside `torch.cuda.graph`.  The sequence, the same for every graph of
+    this package: two eager calls of step on a side stream that has waited for the current one (the warm-up: it raises the
+    dynamic-LDS attributes, which a capture cannot), the current stream waits for the side stream, restore() when given (it undoes
+    what the warm-up did to the state step advances; the captured call is recorded, not run, so the first replay starts where
+    restore left the state), a synchronise, the capture, a synchronise.  Stream, synchronise and graph calls all name `device`: it need
+    not be the current one."""
+    with torch.no_grad(), torch.cuda.device(device):
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                step()
+        torch.cuda.current_stream(device).wait_stream(side)
+        if restore is not None:
+            restore()
+        torch.cuda.synchronize(device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = step()
+    torch.cuda.synchronize(device)
+    return graph, out
+
+
+class LRU(OrderedDict):
+    """a mapping used as a least-recently-used cache: the key looked up last is at the end"""
+
+    def lookup(self, key, build, limit):
+        """self[key], moved to the end; a missing key is built by build() first, and entries past `limit` leave from the front"""
+        if key in self:
+            self.move_to_end(key)
+            return self[key]
+        value = self[key] = build()
+        while len(self) > limit:
+            self.popitem(last=False)
+        return value
+
+
+class Enhancer:
+    """what metrics.evaluate takes as `enhancer`: enhance_device(signal) -> device tensor [length]; called, the same on the host"""
+
+    def __call__(self, noisy_signal, *args, **kw):
+        return self.enhance_device(noisy_signal, *args, **kw).cpu().numpy()
+
+
+def _require_eval(model, who):
+    if model.training:
+        raise RuntimeError(f'{who} needs model.eval(): BatchNorm must use its running statistics')
+
+
+class GraphedEnhancer(Enhancer):
+    """predict() with the whole device-side pipeline (STFT, generator, iSTFT, de-normalisation) captured into HIP graphs (capture),
     one graph per LENGTH BUCKET = number of STFT frames (all lengths that pad to the same multiple of the hop share a
     graph; the reference's wrap-padding to the hop multiple (inference_gan.py:84-87) is done on the host copy, the
     clip scale c of the UNPADDED signal by one eager launch in front of the replay, so results equal predict() exactly).
 
     Batch-1 inference is launch-bound: ~1500 kernel launches cost ~20 ms of host time for ~10 ms of GPU work, a replayed
-    graph removes the host side.  All kernels are launched on torch's current stream, which is the capture stream
-    inside `torch.cuda.graph`; the dynamic-LDS attributes are raised by the eager warm-up run before the capture.
-    `max_graphs` bounds the cache (least recently used bucket is dropped)."""
+    graph removes the host side.  `max_graphs` bounds the cache (least recently used bucket is dropped)."""
 
     def __init__(self, model, config, length=None, device=torch.device('cuda'), max_graphs=8):
         self.model, self.config, self.device, self.max_graphs = model, config, device, max_graphs
-        self.buckets = OrderedDict()          # frames -> dict(graph, static_in, c, out)
+        self.buckets = LRU()                  # frames -> dict(graph, static_in, c, out)
         if length is not None:
-            self._bucket(int(np.ceil(int(length) / config.HOP_SAMPLES)))
+            self._bucket(hop_frames(int(length), config.HOP_SAMPLES)[0])
 
     def _pipeline(self, b):
-        cfg = self.config
-        planes, _ = FE.stft_planes(b['static_in'], cfg.N_FFT, cfg.HOP_SAMPLES, 'pow', scale=b['c'], padded=False)
-        est = self.model.forward_planes(planes)
-        return FE.istft_planes(est, cfg.N_FFT, cfg.HOP_SAMPLES, 'pow') / b['c'][:, None]
+        return spectral_forward(self.model, self.config, b['static_in'], scale=b['c']) / b['c'][:, None]
 
-    def _bucket(self, frames):
-        b = self.buckets.get(frames)
-        if b is not None:
-            self.buckets.move_to_end(frames)
-            return b
+    def _build(self, frames):
         hop = self.config.HOP_SAMPLES
         b = {'static_in': torch.zeros(1, frames * hop, device=self.device, dtype=torch.float32),
              'c': torch.ones(1, device=self.device, dtype=torch.float32)}
         b['static_in'].normal_(0.0, 0.1)             # warm-up on non-degenerate data
-        with torch.no_grad():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._pipeline(b)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            b['graph'] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(b['graph']):
-                b['out'] = self._pipeline(b)
-        torch.cuda.synchronize()
-        self.buckets[frames] = b
-        while len(self.buckets) > self.max_graphs:
-            self.buckets.popitem(last=False)
+        b['graph'], b['out'] = capture(lambda: self._pipeline(b), self.device)
         return b
+
+    def _bucket(self, frames):
+        return self.buckets.lookup(frames, lambda: self._build(frames), self.max_graphs)
 
     @torch.no_grad()
     def enhance_device(self, noisy_signal):
         """the enhanced signal as a device tensor [length], complete on the current stream: a view of the bucket's output buffer,
         valid until the next utterance of the same bucket is enhanced (metrics.evaluate scores it in place)"""
         x = np.asarray(noisy_signal, dtype=np.float32).reshape(-1)
-        length, hop = x.shape[0], self.config.HOP_SAMPLES
-        frames = int(np.ceil(length / hop))
+        length = x.shape[0]
+        frames, pad = hop_frames(length, self.config.HOP_SAMPLES)
         b = self._bucket(frames)
-        pad = frames * hop - length
         xp = np.concatenate([x, x[:pad]]) if pad else x        # the reference's wrap-pad (head of the signal)
         b['static_in'].copy_(torch.from_numpy(xp).reshape(1, -1), non_blocking=True)
         # c = sqrt(L / sum x^2) over the UNPADDED signal: one eager launch writing the scalar the graph reads
         b['c'].copy_(O.clip_scale(b['static_in'][:, :length].contiguous() if pad else b['static_in']))
         b['graph'].replay()
         return torch.flatten(b['out'])[:length]
-
-    def __call__(self, noisy_signal):
-        return self.enhance_device(noisy_signal).cpu().numpy()
 
 
 def check_chunking(chunk, overlap, hop=100):
@@ -138,7 +186,7 @@ def chunk_plan(length, chunk, overlap, hop=100):
     return [(k * (L - S)) // (K - 1) for k in range(K)]
 
 
-class LongEnhancer:
+class LongEnhancer(Enhancer):
     """Enhances recordings of any length: the recording is cut into overlapping chunks (chunk_plan), each chunk is normalised by its
     own c = sqrt(S / sum x^2) -- the statistics of the crops the generator was trained on, not of the whole recording --, the chunks
     run through the generator `batch` at a time (the batched eval forward validate_gan uses), and the enhanced chunks are
@@ -156,36 +204,20 @@ class LongEnhancer:
         self.S, self.V = check_chunking(round(chunk_seconds * rate), round(overlap_seconds * rate), config.HOP_SAMPLES)
         if int(batch) < 1:
             raise ValueError(f'LongEnhancer: batch must be at least 1, got {batch}')
-        self._require_eval(model)
+        _require_eval(model, 'LongEnhancer')
         self.model, self.config, self.batch, self.device = model, config, int(batch), device
         self.forwards = 0               # generator forwards issued so far
 
-    @staticmethod
-    def _require_eval(model):
-        if model.training:
-            raise RuntimeError('LongEnhancer needs model.eval(): BatchNorm must use its running statistics')
-
     def _whole(self, x):
-        """predict() on a device signal [L], result left on the device"""
-        hop, n_fft = self.config.HOP_SAMPLES, self.config.N_FFT
-        noisy = x.unsqueeze(0)
-        c = O.clip_scale(noisy.contiguous())
-        length = noisy.size(-1)
-        padding_len = int(np.ceil(length / hop)) * hop - length
-        noisy = torch.cat([noisy, noisy[:, :padding_len]], dim=-1)
-        planes, _ = FE.stft_planes(noisy, n_fft, hop, 'pow', scale=c, padded=False)
         self.forwards += 1
-        est = self.model.forward_planes(planes)
-        est_audio = FE.istft_planes(est, n_fft, hop, 'pow') / c[:, None]
-        return torch.flatten(est_audio)[:length]
+        return predict_device(self.model, self.config, x)
 
     @torch.no_grad()
     def enhance_chunks(self, x):
         """x: device signal [L], L > S -> (y [K, S], c [K], silent [K], starts [K]): the enhanced chunks still scaled by c (rows of
         silent chunks are zeros), as ops.chunk_assemble takes them"""
-        self._require_eval(self.model)
-        hop, n_fft = self.config.HOP_SAMPLES, self.config.N_FFT
-        plan = chunk_plan(x.numel(), self.S, self.V, hop)
+        _require_eval(self.model, 'LongEnhancer')
+        plan = chunk_plan(x.numel(), self.S, self.V, self.config.HOP_SAMPLES)
         starts = torch.tensor(plan, dtype=torch.int64).to(x.device)
         chunks, c, silent = O.chunk_gather(x, starts, self.S)
         live = torch.nonzero(silent.cpu() == 0).flatten()
@@ -193,24 +225,19 @@ class LongEnhancer:
         live_dev = live.to(x.device)
         for g in range(0, live.numel(), self.batch):
             rows = live_dev[g:g + self.batch]
-            planes, _ = FE.stft_planes(chunks.index_select(0, rows), n_fft, hop, 'pow', scale=c.index_select(0, rows), padded=False)
             self.forwards += 1
-            est = self.model.forward_planes(planes)
-            y.index_copy_(0, rows, FE.istft_planes(est, n_fft, hop, 'pow'))
+            y.index_copy_(0, rows, spectral_forward(self.model, self.config, chunks.index_select(0, rows), scale=c.index_select(0, rows)))
         return y, c, silent, starts
 
     @torch.no_grad()
     def enhance_device(self, noisy_signal):
         """the enhanced recording as a device tensor [length], complete on the current stream"""
-        self._require_eval(self.model)
+        _require_eval(self.model, 'LongEnhancer')
         x = torch.as_tensor(np.asarray(noisy_signal, dtype=np.float32).reshape(-1)).to(self.device)
         if x.numel() <= self.S:
             return self._whole(x)
         y, c, silent, starts = self.enhance_chunks(x)
         return O.chunk_assemble(y, c, silent, starts, self.V, x.numel())
-
-    def __call__(self, noisy_signal):
-        return self.enhance_device(noisy_signal).cpu().numpy()
 
 
 def check_streaming(window, block, lookahead, fade, hop=100):
@@ -239,7 +266,7 @@ def stream_plan(length, block, delay):
     return -(-L // H), D, D + L
 
 
-class StreamEnhancer:
+class StreamEnhancer(Enhancer):
     """Enhances `streams` = B live streams side by side, a block of H samples per stream and step, with a bounded delay.  Per row
     the device keeps a ring of the last W input samples, an int64 sample counter and the withheld tail of the previous estimate
     (include/se_hip.h, "streaming").  A step pushes one block per row:
@@ -256,12 +283,12 @@ class StreamEnhancer:
     select; rows do not interact beyond the rounding of the forward's shared operand scales (eval mode: InstanceNorm is per
     sample, BatchNorm uses its running statistics).  All rows step together; a row without audio in a step is pushed zeros.
 
-    graph=True captures the whole step into ONE HIP graph over static [B, H] input and output buffers (warm-up on a side stream
-    and capture as GraphedEnhancer does; the state is reset after the warm-up): push() is one copy plus one replay.  graph=False
-    issues the same launches eagerly.  Neither path synchronises with the host.  The tensor push() returns is the static output
-    buffer: valid until the next push.  Same contract as LongEnhancer for whole recordings: enhance_device -> device tensor [L]
-    (streams == 1), __call__ -> numpy, so metrics.evaluate(..., enhancer=...) takes it; the last partial block is zero-padded, so
-    the final windows of such an offline run see zeros in their look-ahead."""
+    graph=True captures the whole step into ONE HIP graph over static [B, H] input and output buffers (capture; the state is reset
+    after the warm-up): push() is one copy plus one replay.  graph=False issues the same launches eagerly.  Neither path
+    synchronises with the host.  The tensor push() returns is the static output buffer: valid until the next push.  Same contract
+    as LongEnhancer for whole recordings: enhance_device -> device tensor [L] (streams == 1), __call__ -> numpy, so
+    metrics.evaluate(..., enhancer=...) takes it; the last partial block is zero-padded, so the final windows of such an offline
+    run see zeros in their look-ahead."""
 
     def __init__(self, model, config, window_seconds=2.0, block_seconds=0.1, lookahead_seconds=0.05, fade_seconds=0.01, streams=1,
                  device=torch.device('cuda'), graph=True):
@@ -270,7 +297,7 @@ class StreamEnhancer:
                                                          round(lookahead_seconds * rate), round(fade_seconds * rate), config.HOP_SAMPLES)
         if int(streams) < 1:
             raise ValueError(f'StreamEnhancer: streams must be at least 1, got {streams}')
-        LongEnhancer._require_eval(model)
+        _require_eval(model, 'StreamEnhancer')
         self.model, self.config, self.B, self.device, self.rate = model, config, int(streams), device, rate
         self.delay = self.A + self.V
         self.latency_seconds = (self.H + self.delay) / rate
@@ -286,30 +313,16 @@ class StreamEnhancer:
             self._capture()
 
     def _step(self):
-        cfg = self.config
         O.stream_window(self._in, self.ring, self.pos, self._window, self._c, self._silent)
-        planes, _ = FE.stft_planes(self._window, cfg.N_FFT, cfg.HOP_SAMPLES, 'pow', scale=self._c, padded=False)
-        est = self.model.forward_planes(planes)
-        y = FE.istft_planes(est, cfg.N_FFT, cfg.HOP_SAMPLES, 'pow')
+        y = spectral_forward(self.model, self.config, self._window, scale=self._c)
         O.stream_emit(y, self._c, self._silent, self.tail, self.pos, self.H, self.A, self.V, self._out)
 
     def _capture(self):
-        with torch.no_grad(), torch.cuda.device(self.device):
-            self._in.normal_(0.0, 0.1)                # warm-up on non-degenerate data
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._step()
-            torch.cuda.current_stream().wait_stream(side)
-            self.reset()                              # the warm-up advanced the state
+        def restore():                                # the warm-up advanced the state
+            self.reset()
             self._in.zero_()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._step()
-        torch.cuda.synchronize()
-        self._graph = g
+        self._in.normal_(0.0, 0.1)                    # warm-up on non-degenerate data
+        self._graph, _ = capture(self._step, self.device, restore)
 
     def reset(self, rows=None):
         """forget everything the named rows (default: all) have received: counter, ring row and tail row are zeroed"""
@@ -328,7 +341,7 @@ class StreamEnhancer:
     def push(self, blocks):
         """blocks [B, H] (device tensor or array; [H] with one stream) -> the device tensor [B, H] of enhanced samples that lie D
         behind them, complete on the current stream and valid until the next push"""
-        LongEnhancer._require_eval(self.model)
+        _require_eval(self.model, 'StreamEnhancer')
         if not torch.is_tensor(blocks):
             blocks = torch.from_numpy(np.ascontiguousarray(blocks, dtype=np.float32))
         if blocks.numel() != self.B * self.H or blocks.dim() > 2:
@@ -370,6 +383,3 @@ class StreamEnhancer:
         if self.B != 1:
             raise ValueError(f'StreamEnhancer.enhance_device runs one recording on one stream; this one has {self.B} (use enhance_batch)')
         return self.enhance_batch([noisy_signal])[0]
-
-    def __call__(self, noisy_signal):
-        return self.enhance_device(noisy_signal).cpu().numpy()

@@ -7,18 +7,15 @@ checkpoint_{start..end-1} and names the best epoch.  Without clean files it only
 draw-for-draw equal to a torch.randn_like run.  `-a diffuse*`: diffuse.predict as it is (torch's generator, seeded with --seed).
 Needs a wav reader (scipy.io.wavfile)."""
 import argparse
-import glob
-import os
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from . import metrics
 from .config import get_config
 from .diffuse import DiffuSE, inference_schedule
 from .diffuse import predict as predict_diffuse
-from .inference_gan import _read, _save, format_metrics
+from .inference import Enhancer, load_checkpoint_into
+from .inference_gan import run_cli
 from .sampler import GraphedTSCSampler
 from .tsc_diffusion import TSCNetDiffusion
 
@@ -58,14 +55,10 @@ def load_model(model_path, args, config, device=torch.device('cuda')):
                         config.RESIDUAL_CHANNELS, config.RESIDUAL_LAYERS).to(device)
     else:
         model = TSCNetDiffusion(num_channel=64, num_features=config.N_FFT // 2 + 1, noise_schedule=config.NOISE_SCHEDULE).to(device)
-    checkpoint = torch.load(model_path, map_location=device)
-    sd = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in checkpoint['state_dict'].items())
-    model.load_state_dict(sd)
-    model.eval()
-    return model
+    return load_checkpoint_into(model, model_path, 'state_dict', device)
 
 
-class _DiffuseEnhancer:
+class _DiffuseEnhancer(Enhancer):
     """diffuse.predict behind the `enhance_device` interface of metrics.evaluate (the result goes back to the device for scoring)"""
 
     def __init__(self, model, config, fast, device):
@@ -86,43 +79,12 @@ def build_enhancer(args, config, model_path, device):
     return model, _DiffuseEnhancer(model, config, args.fast, device)
 
 
-def inference(args, config, model_path, data_paths, device):
-    """inference_diffuse.py:271-309: the six metric sums over the test set for one checkpoint"""
-    model, enhancer = build_enhancer(args, config, model_path, device)
-    noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
-    pairs = ((_read(p, config), _read(p.replace(noisy_dir, clean_dir), config)) for p in data_paths)
-    save = (lambda i, est: _save(args, config, data_paths[i], est.cpu().numpy())) if args.save else None
-    return metrics.evaluate(model, config, pairs, on_enhanced=save, enhancer=enhancer)
-
-
 def main(argv=None):
     args, config = parse_option(argv)
     device = torch.device('cuda', args.gpu)
-    os.makedirs(args.output, exist_ok=True)
-    noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
-    data_paths = sorted(glob.glob(f'{noisy_dir}/*.wav'))
-    num = len(data_paths)
     with torch.cuda.device(device):
-        if not all(os.path.exists(p.replace(noisy_dir, clean_dir)) for p in data_paths) or not os.path.isdir(clean_dir):
-            print(f'no clean signals under DATA.TEST_CLEAN_DIR ({clean_dir}): enhancing only, no metrics')
-            _, enhancer = build_enhancer(args, config, args.model_path, device)
-            for path in data_paths:
-                y = enhancer.enhance_device(_read(path, config))
-                if args.save:
-                    _save(args, config, path, y.cpu().numpy())
-            return
-        if args.validate_epochs:
-            best_pesq, best_epoch = 0, 0
-            for epoch in range(args.start, args.end):
-                model_path = os.path.join(args.model_path, 'checkpoint_{:04d}.pth.tar'.format(epoch))
-                avg = inference(args, config, model_path, data_paths, device) / num
-                print('Epoch: {}'.format(epoch))
-                print(format_metrics(avg))
-                if avg[0] > best_pesq:
-                    best_pesq, best_epoch = avg[0], epoch
-            print(f'Best epoch: {best_epoch}\t best PESQ: {best_pesq}')
-        else:
-            print(format_metrics(inference(args, config, args.model_path, data_paths, device) / num))
+        run_cli(args, config, lambda model_path: build_enhancer(args, config, model_path, device),
+                lambda model, enhancer, x: enhancer.enhance_device(x))
 
 
 if __name__ == '__main__':

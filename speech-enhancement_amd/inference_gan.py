@@ -92,6 +92,7 @@ def _read(path, config):
 
 def _save(args, config, path, y):
     from scipy.io import wavfile
+    y = y.cpu() if torch.is_tensor(y) else y
     wavfile.write(os.path.join(args.output, os.path.basename(path)), config.SAMPLE_RATE, np.asarray(y, dtype=np.float32))
 
 
@@ -101,44 +102,51 @@ def format_metrics(avg):
             f'ssnr: {avg[4]:.3f}\t stoi: {avg[5]:.3f}')
 
 
-def inference(args, config, model_path, data_paths, device):
-    """inference_gan.py:102-127: the six metric sums over the test set for one checkpoint"""
-    model = load_model(model_path, config, device)
-    noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
-    pairs = ((_read(p, config), _read(p.replace(noisy_dir, clean_dir), config)) for p in data_paths)
-    save = (lambda i, est: _save(args, config, data_paths[i], est.cpu().numpy())) if args.save else None
-    return metrics.evaluate(model, config, pairs, on_enhanced=save, enhancer=long_enhancer(args, config, model, device))
-
-
-def main(argv=None):
-    args, config = parse_option(argv)
-    device = torch.device('cuda', args.gpu)
+def run_cli(args, config, build, enhance):
+    """the loop of inference_gan.py:102-162, shared with inference_diffuse.  build(model_path) -> (model, enhancer), the enhancer as
+    metrics.evaluate takes it (None: its whole-utterance default).  enhance(model, enhancer, x) -> the enhanced signal of one file,
+    used where there are no clean files to score against."""
     os.makedirs(args.output, exist_ok=True)
     noisy_dir, clean_dir = config.DATA.TEST_NOISY_DIR, config.DATA.TEST_CLEAN_DIR
     data_paths = sorted(glob.glob(f'{noisy_dir}/*.wav'))
     num = len(data_paths)
     if not all(os.path.exists(p.replace(noisy_dir, clean_dir)) for p in data_paths) or not os.path.isdir(clean_dir):
         print(f'no clean signals under DATA.TEST_CLEAN_DIR ({clean_dir}): enhancing only, no metrics')
-        model = load_model(args.model_path, config, device)
-        chunked = long_enhancer(args, config, model, device)
+        model, enhancer = build(args.model_path)
         for path in data_paths:
-            x = _read(path, config)
-            y = chunked(x) if chunked is not None else predict(model, config, x, device)
+            y = enhance(model, enhancer, _read(path, config))
             if args.save:
                 _save(args, config, path, y)
         return
+
+    def average(model_path):
+        """inference_gan.py:102-127: the six metrics over the test set for one checkpoint"""
+        model, enhancer = build(model_path)
+        pairs = ((_read(p, config), _read(p.replace(noisy_dir, clean_dir), config)) for p in data_paths)
+        save = (lambda i, est: _save(args, config, data_paths[i], est)) if args.save else None
+        return metrics.evaluate(model, config, pairs, on_enhanced=save, enhancer=enhancer) / num
     if args.validate_epochs:
         best_pesq, best_epoch = 0, 0
         for epoch in range(args.start, args.end):
-            model_path = os.path.join(args.model_path, 'checkpoint_{:04d}.pth.tar'.format(epoch))
-            avg = inference(args, config, model_path, data_paths, device) / num
+            avg = average(os.path.join(args.model_path, 'checkpoint_{:04d}.pth.tar'.format(epoch)))
             print('Epoch: {}'.format(epoch))
             print(format_metrics(avg))
             if avg[0] > best_pesq:
                 best_pesq, best_epoch = avg[0], epoch
         print(f'Best epoch: {best_epoch}\t best PESQ: {best_pesq}')
     else:
-        print(format_metrics(inference(args, config, args.model_path, data_paths, device) / num))
+        print(format_metrics(average(args.model_path)))
+
+
+def main(argv=None):
+    args, config = parse_option(argv)
+    device = torch.device('cuda', args.gpu)
+
+    def build(model_path):
+        model = load_model(model_path, config, device)
+        return model, long_enhancer(args, config, model, device)
+    # without clean files and without --chunk-len / --stream-block: the eager predict, no graph
+    run_cli(args, config, build, lambda model, enh, x: enh(x) if enh is not None else predict(model, config, x, device))
 
 
 if __name__ == '__main__':

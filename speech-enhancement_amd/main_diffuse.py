@@ -26,7 +26,7 @@ from .config import get_config
 from .optim import build_optimizer
 from .train_diffuse import train_tsc_diffusion, validate_tsc_diffusion
 from .tsc_diffusion import TSCNetDiffusion
-from .utils import kaiming_init, save_checkpoint
+from .utils import kaiming_init, save_checkpoint, strip_module_prefix
 
 model_names = ['diffuse', 'tsc-diffuse']
 
@@ -90,10 +90,6 @@ def check_supported(args):
                            '--multiprocessing-distributed)')
 
 
-def _strip(sd):
-    return {(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()}
-
-
 def _fresh_scaler_state():
     """the state of an untouched GradScaler: the reference's --resume reads checkpoint['scaler']; training here is fp32 and has none"""
     with warnings.catch_warnings():
@@ -114,7 +110,7 @@ def main_worker(gpu, args, config):
         if os.path.isfile(args.resume):
             ck = torch.load(args.resume, map_location=f'cuda:{args.gpu}')
             args.start_epoch = ck['epoch']
-            model.load_state_dict(_strip(ck['state_dict']))
+            model.load_state_dict(strip_module_prefix(ck['state_dict']))
             optimizer.load_state_dict(ck['optimizer'])
             best_loss = ck['best_loss']             # (ck['scaler'] belongs to the reference's fp16 loop: ignored)
             print("=> loaded checkpoint '{}' (epoch {})".format(args.resume, ck['epoch']))

@@ -27,7 +27,7 @@ from .discriminator import Discriminator
 from .generator import TSCNet
 from .optim import build_optimizer
 from .train import attach_data_parallel, train_gan, validate_gan
-from .utils import kaiming_init, save_checkpoint
+from .utils import kaiming_init, save_checkpoint, strip_module_prefix
 
 model_names = ['cmgan', 'scp', 'cp', 'sc']
 DATASET_FACTORY = None
@@ -160,9 +160,8 @@ def main_worker(gpu, ngpus_per_node, args, config):
     if args.resume and os.path.isfile(args.resume):
         ck = torch.load(args.resume, map_location=f'cuda:{args.gpu}')
         args.start_epoch = ck['epoch']
-        strip = lambda sd: {(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()}
-        model.load_state_dict(strip(ck['gen_state_dict']))
-        discriminator.load_state_dict(strip(ck['disc_state_dict']))
+        model.load_state_dict(strip_module_prefix(ck['gen_state_dict']))
+        discriminator.load_state_dict(strip_module_prefix(ck['disc_state_dict']))
         optimizer.load_state_dict(ck['optimizer'])
         optimizer_disc.load_state_dict(ck['optimizer_disc'])
         best_loss = ck['best_loss']

@@ -8,8 +8,6 @@ embedding from a table computed once, so ONE reverse step is captured as a HIP g
 
 The noise is the sampler's own: outputs differ draw-for-draw from a torch.randn_like run and are reproducible per seed.  With
 `noises` supplied the sampler computes what predict_tsc computes with the same `noises`."""
-from collections import OrderedDict
-
 import numpy as np
 import torch
 
@@ -17,6 +15,7 @@ from . import _lib as L
 from . import frontend as FE
 from . import ops as O
 from .diffuse import inference_schedule
+from .inference import LRU, Enhancer, capture, hop_frames, spectral_forward
 from .tsc_diffusion import step_embedding
 
 GAMMA = 0.2                     # inference_diffuse.py:248
@@ -94,10 +93,10 @@ def philox_normal(seed, c2, c3, first_group, n_groups, words=False, normals=True
     return w, z
 
 
-class GraphedTSCSampler:
+class GraphedTSCSampler(Enhancer):
     """predict_tsc with ONE reverse step (STFT of the current audio, the hybrid generator, iSTFT, se_sampler_update,
-    se_sampler_advance) captured into a HIP graph per LENGTH BUCKET = number of STFT frames, replayed `steps` times per utterance;
-    the same graph serves any schedule length.  Per utterance the host copies the signal in, launches the clip scale, the wrap-pad
+    se_sampler_advance) captured into a HIP graph (inference.capture) per LENGTH BUCKET = number of STFT frames, replayed `steps`
+    times per utterance; the same graph serves any schedule length.  Per utterance the host copies the signal in, launches the clip scale, the wrap-pad
     and the STFT of the conditioning spectrum eagerly, then only replays.
 
     State shared by all buckets (device): n = index of the next reverse step (steps - 1 between utterances), run = utterances
@@ -110,7 +109,7 @@ class GraphedTSCSampler:
         self.model, self.config, self.fast, self.max_graphs = model, config, bool(fast), max_graphs
         self.device = torch.device(device)
         self.comp = getattr(args, 'comp_type', 'pow')
-        self.buckets = OrderedDict()          # (frames, supplied noise) -> dict(graph, audio, noisy, orig_planes, c, noise)
+        self.buckets = LRU()                  # (frames, supplied noise) -> dict(graph, audio, noisy, orig_planes, c, noise)
         dev = self.device
         self.n = torch.zeros(1, device=dev, dtype=torch.int32)
         self.run = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -148,10 +147,7 @@ class GraphedTSCSampler:
         self.run.zero_()
 
     def _step(self, b):
-        cfg = self.config
-        planes, _ = FE.stft_planes(b['audio'], cfg.N_FFT, cfg.HOP_SAMPLES, self.comp, padded=False)
-        est = self.model.forward_planes(planes, b['orig_planes'], None, d=self.d)
-        eps = FE.istft_planes(est, cfg.N_FFT, cfg.HOP_SAMPLES, self.comp)
+        eps = spectral_forward(self.model, self.config, b['audio'], b['orig_planes'], None, comp=self.comp, d=self.d)
         sampler_update(b['audio'], b['noisy'], eps, self.coef, self.n, noise=b['noise'], seed=self.seed, run=self.run, c_inv=b['c'],
                        gamma=GAMMA, clamp=False)
         sampler_advance(self.n, self.run, self.emb, self.d)
@@ -161,12 +157,7 @@ class GraphedTSCSampler:
         planes, _ = FE.stft_planes(b['noisy'], cfg.N_FFT, cfg.HOP_SAMPLES, self.comp, padded=False)
         return planes
 
-    def _bucket(self, frames, supplied):
-        key = (frames, bool(supplied))
-        b = self.buckets.get(key)
-        if b is not None:
-            self.buckets.move_to_end(key)
-            return b
+    def _build(self, frames, supplied):
         hop, dev = self.config.HOP_SAMPLES, self.device
         Lp = frames * hop
         b = {'audio': torch.zeros(1, Lp, device=dev, dtype=torch.float32), 'noisy': torch.zeros(1, Lp, device=dev, dtype=torch.float32),
@@ -177,24 +168,16 @@ class GraphedTSCSampler:
         with torch.no_grad():
             b['orig_planes'] = self._conditioner(b).clone()
             n0, run0 = self.n.clone(), self.run.clone()
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._step(b)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.n.copy_(n0)                         # the warm-up leaves the step index, its embedding and the counter as they were
+
+        def restore():                               # the warm-up leaves the step index, its embedding and the counter as they were
+            self.n.copy_(n0)
             self.run.copy_(run0)
             self.d.copy_(self.emb[self.steps - 1:self.steps])
-            torch.cuda.synchronize(dev)
-            b['graph'] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(b['graph']):
-                self._step(b)
-        torch.cuda.synchronize(dev)
-        self.buckets[key] = b
-        while len(self.buckets) > self.max_graphs:
-            self.buckets.popitem(last=False)
+        b['graph'], _ = capture(lambda: self._step(b), dev, restore)
         return b
+
+    def _bucket(self, frames, supplied):
+        return self.buckets.lookup((frames, bool(supplied)), lambda: self._build(frames, bool(supplied)), self.max_graphs)
 
     @torch.no_grad()
     def enhance_device(self, noisy_signal, noises=None):
@@ -202,8 +185,8 @@ class GraphedTSCSampler:
         valid until the same bucket is used again (metrics.evaluate scores it in place)"""
         x = np.ascontiguousarray(np.asarray(noisy_signal, dtype=np.float32).reshape(1, -1))
         length, hop = x.shape[1], self.config.HOP_SAMPLES
-        frames = int(np.ceil(length / hop))
-        if frames * hop - length > length:
+        frames, pad = hop_frames(length, hop)
+        if pad > length:
             raise L.SeHipError(f'sampler: a signal of {length} samples is shorter than its padding to the hop ({hop})')
         with torch.cuda.device(self.device):
             b = self._bucket(frames, noises is not None)
@@ -220,6 +203,3 @@ class GraphedTSCSampler:
             for _ in range(self.steps):
                 b['graph'].replay()
         return torch.flatten(b['audio'])[:length]
-
-    def __call__(self, noisy_signal, noises=None):
-        return self.enhance_device(noisy_signal, noises).cpu().numpy()

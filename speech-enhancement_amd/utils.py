@@ -35,6 +35,12 @@ def kaiming_init(m):
             m.bias.data.fill_(0.01)
 
 
+def strip_module_prefix(state_dict):
+    """the state dict without the 'module.' DDP puts in front of every key (main_gan.py:142); keys without it stay as they are,
+    so checkpoints of one-GPU runs load as well"""
+    return {(k[7:] if k.startswith('module.') else k): v for k, v in state_dict.items()}
+
+
 def save_checkpoint(state, path, is_best, filename='checkpoint.pth.tar'):
     """utils/utils.py:68-75."""
     os.makedirs(path, exist_ok=True)

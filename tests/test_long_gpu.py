@@ -233,3 +233,13 @@ def test_short_recording_is_predict_bit_for_bit(P, model):
     got = enh(x)
     want = P.predict(model, CFG, x)
     assert got.shape == want.shape == (1657,) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize('L', [1657, 1600], ids=['wrap-padded', 'hop-multiple'])
+def test_predict_device_is_predict_bit_for_bit(P, model, L):
+    from speech_enhancement_amd.inference import predict_device
+    x = signal(8, L)
+    got = predict_device(model, CFG, dev(x))
+    assert got.is_cuda and got.shape == (L,)
+    got, want = got.cpu().numpy(), P.predict(model, CFG, x)
+    assert want.shape == (L,) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
